@@ -16,10 +16,28 @@ on several):
       (bench_score.run_c5; metric: scored windows/s)
 ``--model/--dim/--batch`` override the chosen config's fields.
 
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) sets up, warms up,
+times the K steps of the headline workload and prints the result line:
+``metric`` / ``value`` / ``unit`` / ``higher_is_better`` / ``dtype`` /
+``ms_per_step`` (milliseconds per timed step) and the workload description.
+``--full`` adds everything else described below (per-step spread, kernel probes
+and rooflines, the CPU baseline, the c2 / c3_f32 sub-objects, the N>1
+same-workload run); each of those takes runs of its own after the timed region.
+
+``--dump-outputs DIR`` (one GPU) writes what the last timed step handed back as
+``DIR/<name>.npy`` (float32): the step's loss, the BatchNorm running statistics
+and a fixed seeded sample (DUMP_SAMPLE elements, the same indices for all three)
+of the fp32 master parameters and the two Adam moments; c5 writes the BASE and
+SAP score of every window.  The timed steps always start from the model state
+the W warm-up steps left (the time-sized soak's updates are rolled back before
+the timed region), on the same seeded batches, so two runs with the same
+arguments feed every timed step the same inputs.
+
 ``python bench.py --gpus N`` without torchrun env vars spawns the N ranks itself
 (torch.multiprocessing, before any GPU call); under torchrun it reads
 RANK/WORLD_SIZE/LOCAL_RANK.  W untimed steps, then K timed steps between
-barrier + synchronize pairs, the max over ranks; rank 0 prints ONE JSON line:
+barrier + synchronize pairs, the max over ranks; rank 0 prints ONE JSON line.
+With ``--full`` the line also holds:
 
 * the timed steps are eager executor steps (mmad_ae_train_step: one host
   call enqueues the whole step on the main + side streams, no host sync);
@@ -342,6 +360,11 @@ def parse_args(argv=None):
     ap.add_argument("--dim", type=int)
     ap.add_argument("--batch", type=int, help="windows per GPU per step")
     ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-step spread, kernel "
+                         "probes / rooflines, CPU baseline, c2 and c3_f32 sub-objects, N>1 same-workload run")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (one GPU)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-probe", action="store_true", help="skip the in-situ kernel probe")
@@ -383,6 +406,8 @@ def run(args):
     # configs[2], which is also C4's per-GPU shard, where the 1/2/4/8 curve
     # starts); c4 on several
     cname = args.config if args.config != "auto" else ("c3" if world == 1 else "c4")
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs is a one-GPU option")
     for kv in args.tune:
         k, v = kv.split("=", 1)
         _native.tune_set(k, int(v))
@@ -398,8 +423,8 @@ def run(args):
     for k in ("model", "dim", "batch"):
         if getattr(args, k) is not None:
             cfgd[k] = getattr(args, k)
-    res, model = train_workload(args, cname, cfgd, rank, world, local, with_cpu=True)
-    if (rank == 0 and world == 1 and args.config == "auto" and not args.no_c2
+    res, model = train_workload(args, cname, cfgd, rank, world, local, with_cpu=True, dump=True)
+    if (args.full and rank == 0 and world == 1 and args.config == "auto" and not args.no_c2
             and all(getattr(args, k) is None for k in ("model", "dim", "batch"))):
         # the smaller BASELINE configs[1] in the same line, so the c2 series of
         # earlier rounds stays comparable (same steps / warmup, its own probes)
@@ -434,9 +459,59 @@ def run(args):
         dist.destroy_process_group()
 
 
-def train_workload(args, cname, cfgd, rank, world, local, with_cpu):
+DUMP_SAMPLE = 1 << 21     # elements of each large buffer --dump-outputs writes
+DUMP_SEED = 20210530
+
+
+def snapshot_state(model):
+    """Everything a train step updates: the fp32 master parameters, the Adam
+    moments and step count, the BatchNorm running statistics, the noise
+    offset.  (The bf16 weight shadow is rebuilt from the master on restore.)"""
+    nat = model._native
+    return ([t.clone() for t in (nat.params, nat.exp_avg, nat.exp_avg_sq, nat.running)],
+            nat.adam_step_count, model._rng_offset)
+
+
+def restore_state(model, state):
+    nat = model._native
+    bufs, nat.adam_step_count, model._rng_offset = state
+    for t, s in zip((nat.params, nat.exp_avg, nat.exp_avg_sq, nat.running), bufs):
+        t.copy_(s)
+    nat.sync_shadow(force=True)
+
+
+def save_outputs(out_dir, arrays):
+    """DIR/<name>.npy, float32 (numpy or device arrays)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def dump_train_outputs(out_dir, nat, loss):
+    """What the last timed train step handed back: its loss and the updated
+    model / optimizer state.  The three n_params-sized buffers are sampled at
+    the same DUMP_SAMPLE fixed, seeded positions (the whole buffer when it is
+    smaller)."""
+    import numpy as np
+    import torch
+    n = nat.n_params
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(nat.device)
+        pick = lambda t: t[idx]   # noqa: E731
+    else:
+        pick = lambda t: t        # noqa: E731
+    save_outputs(out_dir, {"loss": loss, "params": pick(nat.params), "adam_exp_avg": pick(nat.exp_avg),
+                           "adam_exp_avg_sq": pick(nat.exp_avg_sq), "bn_running": nat.running})
+
+
+def train_workload(args, cname, cfgd, rank, world, local, with_cpu, dump=False):
     """W untimed + K timed train steps of one workload; returns (result dict,
-    model).  The probes and the CPU baseline run after the timed region."""
+    model).  With --full the probes and the CPU baseline run after the timed
+    region.  dump: this is the workload --dump-outputs writes."""
     import types
     import torch
     import torch.distributed as dist
@@ -466,6 +541,10 @@ def train_workload(args, cname, cfgd, rank, world, local, with_cpu):
     for i in range(args.warmup):
         model.train_step_async(pool[i % len(pool)], opt)
     torch.cuda.synchronize()
+    # one GPU: the state the W warm-up steps left, put back before the timed
+    # region -- the soak below is sized by time, so the number of updates it
+    # applies differs from run to run
+    state0 = snapshot_state(model) if world == 1 else None
     tw = time.perf_counter()                     # step time for the soak's length
     for i in range(10):
         model.train_step_async(pool[i % len(pool)], opt)
@@ -483,13 +562,17 @@ def train_workload(args, cname, cfgd, rank, world, local, with_cpu):
     for i in range(soak):
         model.train_step_async(pool[i % len(pool)], opt)
     torch.cuda.synchronize()
+    if state0 is not None:
+        restore_state(model, state0)
+        del state0
+        torch.cuda.synchronize()
     probe_layer = pick_dominant_layer(nat, batch)
     lib = _native.load()
     # the dominant dW launch timed inside the timed steps themselves: events
     # attached to that one launch (hipExtLaunchKernel start / stop, no marker
     # packet, no wait for the side stream; mmad_ae_probe kind 3), read after
     # the timed region
-    probe_timed = not args.no_probe and rank == 0 and not nat.use_graph and args.steps > 0
+    probe_timed = args.full and not args.no_probe and rank == 0 and not nat.use_graph and args.steps > 0
     n_cap = min(args.steps, 4096)              # the executor's probe capacity limit: the first 4096 steps
     if probe_timed:
         _native.check(lib.mmad_ae_probe(nat._h, 3, probe_layer, n_cap), "mmad_ae_probe")
@@ -521,6 +604,8 @@ def train_workload(args, cname, cfgd, rank, world, local, with_cpu):
     if bad:
         raise SystemExit("bench: a kernel barrier timed out in the timed steps; no valid measurement")
     loss_v = float(loss.item())
+    if args.dump_outputs and dump:
+        dump_train_outputs(args.dump_outputs, nat, loss)
     durs_timed, layers_timed = [], None
     if probe_timed:
         import ctypes
@@ -568,21 +653,22 @@ def train_workload(args, cname, cfgd, rank, world, local, with_cpu):
     }
     if args.tune:
         res["tune"] = args.tune
-    # per-step spread: the same number of steps again, a HIP event after each
-    # (on the caller's stream, which joins the side streams at every step end)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    evs[0].record()
-    for i in range(args.steps):
-        model.train_step_async(pool[i % len(pool)], opt)
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
-    q = lambda f: per[min(len(per) - 1, int(f * len(per)))]   # noqa: E731
-    res["step_spread"] = {"median_ms": round(q(0.5), 4), "p10_ms": round(q(0.1), 4),
-                          "p90_ms": round(q(0.9), 4), "max_ms": round(per[-1], 4),
-                          "steps": args.steps,
-                          "how": "HIP event after every step, separate run right after the timed one"}
-    if world > 1:
+    if args.full:
+        # per-step spread: the same number of steps again, a HIP event after each
+        # (on the caller's stream, which joins the side streams at every step end)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        evs[0].record()
+        for i in range(args.steps):
+            model.train_step_async(pool[i % len(pool)], opt)
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
+        q = lambda f: per[min(len(per) - 1, int(f * len(per)))]   # noqa: E731
+        res["step_spread"] = {"median_ms": round(q(0.5), 4), "p10_ms": round(q(0.1), 4),
+                              "p90_ms": round(q(0.9), 4), "max_ms": round(per[-1], 4),
+                              "steps": args.steps,
+                              "how": "HIP event after every step, separate run right after the timed one"}
+    if args.full and world > 1:
         # same workload without the exchange, same ranks (read scaling against it)
         mdl_dist = model.dist
         model.dist = None
@@ -605,7 +691,7 @@ def train_workload(args, cname, cfgd, rank, world, local, with_cpu):
                                    "how": "same ranks, exchange off, after the timed region (max over ranks)"}
         model.dist = mdl_dist
     durs, n_probe, probe_layers, fwd_in_step = [], 0, None, []
-    if not args.no_probe and rank == 0:
+    if args.full and not args.no_probe and rank == 0:
         # the same launch once more, isolated: eager steps of the same state
         # and inputs right after the timed region, each probed launch started
         # only once the side stream's earlier work is done (a HIP event pair
@@ -652,7 +738,7 @@ def train_workload(args, cname, cfgd, rank, world, local, with_cpu):
     res["train_step"] = ("one captured hipGraph replay per step (mmad_ae_train_step_graph)"
                          if nat.use_graph and (model.dist is None or not model.dist.native)
                          else "eager executor step (mmad_ae_train_step)")
-    if rank == 0:
+    if args.full and rank == 0:
         if durs_timed or durs:
             # fused steps (Adam in the dW epilogue): the timed steps' own
             # launches when they were probed, else the isolated probe steps

@@ -10,7 +10,7 @@ cp $L /tmp/libmmad_build.so
 for lib in old new old new old new; do
   cp tools/ab/libmmad_$lib.so $L
   echo "== $lib" >> $O/${T}_ab.jsonl
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline "$@" 2>>$O/${T}_err.log | tail -1 >> $O/${T}_ab.jsonl || exit 1
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline "$@" 2>>$O/${T}_err.log | tail -1 >> $O/${T}_ab.jsonl || exit 1
 done
 cp tools/ab/libmmad_new.so $L
 timeout -k 10 300 rocprofv3 --kernel-trace -d /tmp/${T}_prof -o run -- python3 bench.py --no-c2 --no-cpu-baseline --steps 20 --soak-s 0.5 > $O/${T}_prof.log 2>&1 || exit 1

@@ -10,7 +10,7 @@ for i in $(seq $N); do
   for lib in old new; do
     cp tools/ab/libmmad_$lib.so $L
     echo "== $lib" >> $O/${T}_ab.jsonl
-    timeout -k 10 200 python3 bench.py --no-cpu-baseline "$@" 2>>$O/${T}_err.log | tail -1 >> $O/${T}_ab.jsonl || exit 1
+    timeout -k 10 200 python3 bench.py --full --no-cpu-baseline "$@" 2>>$O/${T}_err.log | tail -1 >> $O/${T}_ab.jsonl || exit 1
   done
 done
 cp /tmp/libmmad_build.so $L

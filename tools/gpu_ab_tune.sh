@@ -6,6 +6,6 @@ O=gpurun_out
 for r in $(seq $R); do
   for v in $VALS; do
     echo "== $K=$v" >> $O/${T}_tune_ab.jsonl
-    timeout -k 10 200 python3 bench.py --no-cpu-baseline --tune $K=$v "$@" 2>>$O/${T}_err.log | tail -1 >> $O/${T}_tune_ab.jsonl || exit 1
+    timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --tune $K=$v "$@" 2>>$O/${T}_err.log | tail -1 >> $O/${T}_tune_ab.jsonl || exit 1
   done
 done

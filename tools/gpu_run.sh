@@ -4,7 +4,7 @@
 #   tests            full `pytest -m gpu` suite
 #   tests:<expr>     `pytest -m gpu -k <expr>` ('+' -> ' ', e.g. tests:bn_fused+or+dp)
 #   smoke            __graft_entry__.smoke()
-#   bench[:<args>]   python bench.py <args, commas -> spaces>
+#   bench[:<args>]   python bench.py <args, commas -> spaces>  (--full: rooflines, sub-objects, CPU baseline)
 #   prof[:<args>]    rocprofv3 --kernel-trace --stats of bench.py <args>
 #   py:<script,args> python <script> <args>          (tools/*.py helpers)
 #   bin:<path,args>  a prebuilt binary (tools/ubench_*)
