@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("MMAD_LIB", os.path.join(HERE, "libmmad.so"))
 MMAD_OK = 0
 MMAD_EINVAL, MMAD_EUNSUPPORTED, MMAD_EHIP, MMAD_ERCCL = -1, -2, -3, -4
 F32, BF16 = 0, 1
+BF16X3 = 2   # split-bf16 planes: eval / score path only (include/mmad.h)
 ACT = {None: 0, "leakyrelu": 1, "relu": 2, "sigmoid": 3, "tanh": 4}
 
 _P = ctypes.c_void_p
@@ -55,6 +56,7 @@ SIGNATURES = {
     "mmad_mse_loss_ws_floats": (_I, []),
     "mmad_mse_loss": (_I, [_I64, _P, _P, _I, _P, _P, _P]),
     "mmad_mse_grad": (_I, [_I64, _P, _P, _P, _I, _P, _P, _P]),
+    "mmad_split_planes": (_I, [_I64, _P, _P, _P, _P]),
     "mmad_pack_input": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "mmad_unpack_output": (_I, [_I, _I, _I, _I, _P, _P, _I, _P]),
     "mmad_adam": (_I, [_I64, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P, _I64, _P]),
@@ -68,6 +70,8 @@ SIGNATURES = {
     "mmad_ae_bind": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "mmad_ae_sync_shadow": (_I, [_P, _P]),
     "mmad_ae_set_shadow_pair": (_I, [_P, _P]),
+    "mmad_ae_set_score_planes": (_I, [_P, _P]),
+    "mmad_ae_score_dtype": (_I, [_P]),
     "mmad_ae_current_shadow": (_P, [_P]),
     "mmad_ae_train_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _P, _U64, _U64, _F, _P, _P, _I64, _P]),
     "mmad_ae_train_step": (_I, [_P, _P, _I, _I, _I, _P, _U64, _U64, _F, _F, _F, _F, _F, _I, _P,

@@ -110,9 +110,13 @@ class AutoEncoder(AbstractModel):
 
     Extra (build) arguments: ``dtype`` ('f32' exact parity path, 'bf16'
     throughput path), ``vib`` (encoder emits mu|logvar, decoder consumes a
-    k-sample reparameterised z; SURVEY §8 a10/a10'), ``k``, ``beta_kl``."""
+    k-sample reparameterised z; SURVEY §8 a10/a10'), ``k``, ``beta_kl``,
+    ``score_dtype`` ('bf16x3': an fp32 model's eval forward / validate /
+    get_diffs / score_windows run split-bf16 GEMMs on the bf16 matrix cores,
+    fp32-class numbers; training is untouched)."""
 
-    def __init__(self, encoder, decoder, recon_loss, dtype="f32", vib=False, k=1, beta_kl=1.0):
+    def __init__(self, encoder, decoder, recon_loss, dtype="f32", vib=False, k=1, beta_kl=1.0,
+                 score_dtype=None):
         super().__init__()
         self.encoder = encoder
         self.decoder = decoder
@@ -123,6 +127,13 @@ class AutoEncoder(AbstractModel):
         self.mmad_dtype = dtype
         dev = next(encoder.parameters()).device
         self._native = NativeAE(encoder.widths, decoder.widths, vib=vib, dtype=dtype, device=dev)
+        if score_dtype is not None:
+            if self._native.dt == _native.F32:
+                self._native.set_score_precision(score_dtype)
+            else:
+                import warnings
+                warnings.warn(f"score_dtype={score_dtype!r} is ignored for a dtype='bf16' model: it "
+                              "scores on its bf16 weight shadow")
         self._nbt_pending = 0
         self._rng_offset = 0
         self.dist = None  # set by icra2021_multimodal_ad_amd.dist.attach_data_parallel

@@ -61,6 +61,12 @@ struct mmad_ae {
   // shadow_alt while this step's backward still reads shadow, then the two
   // swap; so a dW GEMM need not wait for its layer's bwd-data GEMM
   void* shadow_alt = nullptr;
+  // split-bf16 scoring (mmad_ae_set_score_planes, F32 handles): bf16
+  // [2][n_weight] weight planes; the eval forward / score GEMMs then run as
+  // MMAD_BF16X3.  planes_stale: the fp32 weights were (or may have been)
+  // written since the last split; the scoring entry points re-split first
+  void* planes = nullptr;
+  bool planes_stale = true;
   // side stream + events for the dW / Adam overlap (created at bind time)
   hipStream_t side = nullptr;
   std::vector<hipEvent_t> ev_fork, ev_data;
@@ -242,6 +248,7 @@ struct mmad_ae {
 struct LayerWS {
   void *out, *y, *dy, *dz;
   float *stats, *mean, *rstd, *scale, *shift, *dbpart, *rowsq;
+  float* ref32;     // x3 scoring: fp32 copy of an encoder layer's pass-1 output (else null)
   double* bnpart;   // fp64 BN-backward column partials [Mp/64][2][Np]
   // consumer of a train-mode BN producer: W*scale (GEMM dtype) and the
   // per-64-column partials of sum_k shift[k] W[n][k]
@@ -377,6 +384,12 @@ static void carve(const mmad_ae* h, int B, int k, char* base, AeWS& w) {
     s.wf = folded ? take((int64_t)a.Np * a.Kp * es) : nullptr;
     s.cpart = folded ? (float*)take((int64_t)(a.Kp / 64) * a.Np * 4) : nullptr;
   }
+  // x3 scoring: the fp32 references of pass 2, after every other buffer (no
+  // existing offset moves when planes are attached or detached)
+  for (int i = 0; i < nL; ++i) {
+    const AeLayer& a = h->L[i];
+    w.l[i].ref32 = (h->planes && a.enc) ? (float*)take((int64_t)w.Mpe * a.Np * 4) : nullptr;
+  }
   w.bytes = (off + 255) / 256 * 256;
 }
 
@@ -503,6 +516,7 @@ int mmad_ae_bind(mmad_ae* h, float* params, float* grads, float* adam_m, float* 
   h->v = adam_v;
   h->shadow = shadow;
   h->running = running;
+  h->planes_stale = true;
   if (!h->side) {
     // lowest priority: the side stream fills CUs the critical chain leaves idle
     int least = 0, greatest = 0;
@@ -553,9 +567,33 @@ int mmad_ae_set_shadow_pair(mmad_ae* h, void* alt) {
 
 const void* mmad_ae_current_shadow(const mmad_ae* h) { return h ? h->shadow : nullptr; }
 
+// dtype of the eval forward / score GEMMs
+static int score_dt(const mmad_ae* h) { return h->planes ? MMAD_BF16X3 : h->dtype; }
+
+// re-split the weight region into the score planes if a weight write may have
+// happened since the last split (one launch on the caller's stream)
+static int refresh_planes(mmad_ae* h, hipStream_t st, bool force = false) {
+  if (!h->planes || !(h->planes_stale || force)) return MMAD_OK;
+  RET_IF(mmad_split_planes(h->n_weight, h->params, h->planes, (char*)h->planes + h->n_weight * 2, st));
+  h->planes_stale = false;
+  return MMAD_OK;
+}
+
+int mmad_ae_set_score_planes(mmad_ae* h, void* planes) {
+  MMAD_CHECK_ARG(h, "ae_set_score_planes: null handle");
+  MMAD_CHECK_ARG(h->dtype == MMAD_F32, "ae_set_score_planes: fp32 handles only (a bf16 handle "
+                 "scores on its own shadow)");
+  MMAD_CHECK_ARG(((uintptr_t)planes) % 16 == 0, "ae_set_score_planes: planes must be 16-byte aligned");
+  h->planes = planes;
+  h->planes_stale = true;
+  return mmad_ae_clear_graphs(h);   // captured passes bake the operand dtype and addresses in
+}
+
+int mmad_ae_score_dtype(const mmad_ae* h) { return h ? score_dt(h) : -1; }
+
 int mmad_ae_sync_shadow(mmad_ae* h, void* stream) {
   MMAD_CHECK_ARG(h && h->params, "ae_sync_shadow: unbound");
-  if (h->dtype != MMAD_BF16) return MMAD_OK;
+  if (h->dtype != MMAD_BF16) return refresh_planes(h, (hipStream_t)stream, true);
   if (h->shadow_alt) RET_IF(mmad_to_bf16(h->n_weight, h->params, h->shadow_alt, stream));
   return mmad_to_bf16(h->n_weight, h->params, h->shadow, stream);
 }
@@ -570,6 +608,13 @@ static void* adam_shadow(const mmad_ae* h, const AeLayer& a, bool ping) {
 static const void* weights(const mmad_ae* h, const AeLayer& a) {
   if (h->dtype == MMAD_BF16) return (const char*)h->shadow + a.w_off * 2;
   return h->params + a.w_off;
+}
+// the weight operand of an eval / score GEMM of dtype dt: for MMAD_BF16X3 the
+// layer's hi plane, with its lo plane (n_weight elements on) set in ep
+static const void* weights_dt(const mmad_ae* h, const AeLayer& a, int dt, GemmEpi& ep) {
+  if (dt != MMAD_BF16X3) return weights(h, a);
+  ep.b_lo = (const char*)h->planes + (h->n_weight + a.w_off) * 2;
+  return (const char*)h->planes + a.w_off * 2;
 }
 
 // input of layer l; in train mode a BN producer's output stays pre-BN (a): the
@@ -718,7 +763,8 @@ static GemmEpi fwd_epi(const mmad_ae* h, const AeWS& w, const AeLayer& a, const 
 // mse_done (nullable): an event the train-mode MSE GEMM launch completes itself
 static int run_forward(mmad_ae* h, AeWS& w, const float* x, int ld_x, int mode, const float* eps,
                        uint64_t seed, uint64_t offset, hipStream_t st, hipEvent_t mse_done = nullptr) {
-  const int dt = h->dtype;
+  const int dt = mode == 1 ? score_dt(h) : h->dtype;
+  const bool x3 = dt == MMAD_BF16X3;
   const int nL = (int)h->L.size();
   const int B = w.B, k = w.k;
   const bool train = mode != 1;
@@ -794,11 +840,19 @@ static int run_forward(mmad_ae* h, AeWS& w, const float* x, int ld_x, int mode, 
       GemmEpi ep = fwd_epi(h, w, a, s, M, s.y, folded);
       ep.bn_scale = s.scale;
       ep.bn_shift = s.shift;
-      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_FWD, in, a.Kp, wt, a.Kp, Mp, a.Np, a.Kp, ep, st, nullptr,
+      const void* we = x3 ? weights_dt(h, a, dt, ep) : wt;
+      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_FWD, in, a.Kp, we, a.Kp, Mp, a.Np, a.Kp, ep, st, nullptr,
                      PROBE_FWD + l));
     } else {
       GemmEpi ep = fwd_epi(h, w, a, s, M, s.out, folded);
-      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_FWD, in, a.Kp, wt, a.Kp, Mp, a.Np, a.Kp, ep, st, nullptr,
+      const void* we = x3 ? weights_dt(h, a, dt, ep) : wt;
+      if (x3 && l == nL - 1) {
+        // x_hat also in fp32 (the layer's unused dy buffer): mmad_ae_forward
+        // unpacks / reduces that copy, not the re-rounded planes
+        ep.out32 = (float*)s.dy;
+        ep.ld32 = a.Np;
+      }
+      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_FWD, in, a.Kp, we, a.Kp, Mp, a.Np, a.Kp, ep, st, nullptr,
                      PROBE_FWD + l));
     }
     if (h->vib && l == h->n_enc - 1) {
@@ -1244,6 +1298,7 @@ int mmad_ae_train_step(mmad_ae* h, const float* x, int ld_x, int B, int k, const
                  "ae_train_step: unbound handle");
   MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && loss_out, "ae_train_step: bad input");
   MMAD_CHECK_ARG(step >= 1, "ae_train_step: step must be >= 1");
+  h->planes_stale = true;
   AeWS w;
   RET_IF(prepare_ws(h, B, k, ws, ws_bytes, w, (hipStream_t)stream));
   hipStream_t st = (hipStream_t)stream;
@@ -1288,6 +1343,7 @@ int mmad_ae_train_step_graph(mmad_ae* h, const float* x, int ld_x, int B, int k,
                  "ae_train_step_graph: unbound handle");
   MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && loss_out, "ae_train_step_graph: bad input");
   MMAD_CHECK_ARG(step >= 1, "ae_train_step_graph: step must be >= 1");
+  h->planes_stale = true;
   if (h->comm || h->graph_broken)   // eager schedule for these
     return mmad_ae_train_step(h, x, ld_x, B, k, eps, seed, offset, beta_kl, lr, beta1, beta2,
                               adam_eps, step, loss_out, ws, ws_bytes, stream);
@@ -1435,6 +1491,7 @@ int mmad_ae_dw_plan(const mmad_ae* h, int max_n, int64_t* off, int64_t* n, int* 
 
 int mmad_ae_dp_sync_master(mmad_ae* h, void* stream) {
   MMAD_CHECK_ARG(h && h->params && h->m && h->v, "ae_dp_sync_master: unbound handle");
+  h->planes_stale = true;
   if (!h->comm || !h->master_stale) return MMAD_OK;
   hipStream_t st = (hipStream_t)stream;
   const int nr = mmad_comm_size(h->comm);
@@ -1472,6 +1529,7 @@ int mmad_ae_adam(mmad_ae* h, float lr, float beta1, float beta2, float eps, int 
                  void* stream) {
   MMAD_CHECK_ARG(h && h->params && h->grads && h->m && h->v, "ae_adam: unbound handle");
   MMAD_CHECK_ARG(step >= 1, "ae_adam: step must be >= 1");
+  h->planes_stale = true;
   const AdamHyper ah = adam_hyper(lr, beta1, beta2, eps, step);
   return mmad_adam_w(h->n_params, h->params, h->grads, h->m, h->v, ah.w1, ah.w2, eps, ah.step_size,
                    ah.bc2_sqrt, h->dtype == MMAD_BF16 ? h->shadow : nullptr,
@@ -1482,6 +1540,7 @@ int mmad_ae_adam_range(mmad_ae* h, float lr, float beta1, float beta2, float eps
                        int64_t off, int64_t n, void* stream) {
   MMAD_CHECK_ARG(h && h->params && h->grads && h->m && h->v, "ae_adam_range: unbound handle");
   MMAD_CHECK_ARG(step >= 1, "ae_adam_range: step must be >= 1");
+  h->planes_stale = true;
   MMAD_CHECK_ARG(off >= 0 && n >= 0 && off + n <= h->n_params && off % 4 == 0,
                  "ae_adam_range: bad range [%lld, +%lld)", (long long)off, (long long)n);
   const AdamHyper ah = adam_hyper(lr, beta1, beta2, eps, step);
@@ -1503,9 +1562,12 @@ int mmad_ae_forward(mmad_ae* h, const float* x, int ld_x, int B, int train_bn, f
   AeWS w;
   RET_IF(prepare_ws(h, B, 1, ws, ws_bytes, w, (hipStream_t)stream));
   hipStream_t st = (hipStream_t)stream;
+  const bool x3 = !train_bn && h->planes;
+  if (x3) RET_IF(refresh_planes(h, st));
   RET_IF(run_forward(h, w, x, ld_x, train_bn ? 2 : 1, nullptr, 0x5eed, 0, st));
   const AeLayer& last = h->L.back();
-  const void* xh = w.l.back().out;
+  // (x3: the last GEMM's fp32 copy of x_hat, run_forward)
+  const void* xh = x3 ? w.l.back().dy : w.l.back().out;
   if (x_hat) RET_IF(mmad_unpack_output(h->dtype, B, last.N, last.Np, xh, x_hat, ld_out, st));
   if (loss_out) {
     RET_IF(mmad_sse_partials(h->dtype, B, last.N, last.Np, xh, x, ld_x, w.misc, 256, st));
@@ -1518,7 +1580,12 @@ int mmad_ae_forward(mmad_ae* h, const float* x, int ld_x, int B, int train_bn, f
 // layer_sq + l*ld_sq
 static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq,
                        int64_t ld_sq, float* diffs, AeWS& w, hipStream_t st) {
-  const int dt = h->dtype;
+  // x3 (score planes attached): activations travel as bf16 planes, every
+  // reference of a diff stays fp32 -- pass 1 leaves an fp32 copy of each
+  // encoder output (ref32), the decoder's last layer scores against the
+  // caller's x itself, and the SCORE epilogue subtracts before it rounds
+  const int dt = score_dt(h);
+  const bool x3 = dt == MMAD_BF16X3;
   const int nL = (int)h->L.size();
   RET_IF(mmad_pack_input(dt, B, h->L[0].K, w.Mpe, h->L[0].Kp, x, ld_x, w.xin, st));
   int ld_diff = h->L[0].K;
@@ -1538,18 +1605,21 @@ static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer
       ep.bn_scale = s.scale;
       ep.bn_shift = s.shift;
     }
+    const void* wt = weights_dt(h, a, dt, ep);
     if (l == nL - 1) {
-      ep.ref = w.xin;
-      ep.ldref = a.Np;
+      ep.ref = x3 ? (const void*)x : w.xin;
+      ep.ldref = x3 ? ld_x : a.Np;
       ep.rowsq = s.rowsq;
       ep.ldrow = Mp;
       ep.diff = diffs;
       ep.lddiff = ld_diff;
-      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_SCORE, in, a.Kp, weights(h, a), a.Kp, Mp, a.Np, a.Kp,
-                                ep, st));
+      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_SCORE, in, a.Kp, wt, a.Kp, Mp, a.Np, a.Kp, ep, st));
     } else {
-      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_FWD, in, a.Kp, weights(h, a), a.Kp, Mp, a.Np, a.Kp,
-                                ep, st));
+      if (x3 && a.enc) {
+        ep.out32 = s.ref32;
+        ep.ld32 = a.Np;
+      }
+      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_FWD, in, a.Kp, wt, a.Kp, Mp, a.Np, a.Kp, ep, st));
     }
     if (h->vib && l == h->n_enc - 1) {
       RET_IF(mmad_vib_reparam_fwd(dt, B, h->btl, 1, s.out, a.Np, nullptr, nullptr, 0, 0, 1, w.zbuf,
@@ -1567,14 +1637,14 @@ static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer
       ep.bn_scale = s.scale;
       ep.bn_shift = s.shift;
     }
-    ep.ref = a.bn ? s.y : s.out;
+    ep.ref = x3 ? (const void*)s.ref32 : (a.bn ? s.y : s.out);
     ep.ldref = a.Np;
     ep.rowsq = s.rowsq;
     ep.ldrow = w.Mpe;
     ep.diff = diffs ? diffs + coff : nullptr;
     ep.lddiff = ld_diff;
-    RET_IF(ae_gemm(h, w, dt, GEMM_EPI_SCORE, cur, a.Kp, weights(h, a), a.Kp, w.Mpe, a.Np,
-                              a.Kp, ep, st));
+    const void* wt = weights_dt(h, a, dt, ep);
+    RET_IF(ae_gemm(h, w, dt, GEMM_EPI_SCORE, cur, a.Kp, wt, a.Kp, w.Mpe, a.Np, a.Kp, ep, st));
     coff += a.N;
     cur = s.dy;
   }
@@ -1594,9 +1664,15 @@ int mmad_ae_score(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq, 
                   void* ws, int64_t ws_bytes, void* stream) {
   MMAD_CHECK_ARG(h && h->params && h->running, "ae_score: unbound handle");
   MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && layer_sq, "ae_score: bad args");
+  RET_IF(refresh_planes(h, (hipStream_t)stream));
   AeWS w;
   RET_IF(prepare_ws(h, B, 1, ws, ws_bytes, w, (hipStream_t)stream));
   return score_batch(h, x, ld_x, B, layer_sq, B, diffs, w, (hipStream_t)stream);
+}
+
+// base of the weight operand the score GEMMs read (a captured pass's key)
+static const void* score_weights(const mmad_ae* h) {
+  return h->planes ? (const void*)h->planes : weights(h, h->L[0]);
 }
 
 // the whole N-window pass, batch by batch, on stream st
@@ -1619,10 +1695,13 @@ int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int ba
                  "ae_score_stream: bad args (N=%lld batch=%d ld_sq=%lld)", (long long)N, batch,
                  (long long)ld_sq);
   hipStream_t st = (hipStream_t)stream;
+  // stale score planes are re-split here, on the caller's stream and outside
+  // the captured pass: a replay reads whatever the planes hold when it runs
+  RET_IF(refresh_planes(h, st));
   if (!use_graph) return score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, ws, ws_bytes, st);
   for (auto& g : h->graphs) {
     if (g.x == x && g.ld_x == ld_x && g.N == N && g.batch == batch && g.sq == layer_sq &&
-        g.ld_sq == ld_sq && g.ws == ws && g.wts == weights(h, h->L[0])) {
+        g.ld_sq == ld_sq && g.ws == ws && g.wts == score_weights(h)) {
       MMAD_HIP_CHECK(hipGraphLaunch(g.exec, st));
       return MMAD_OK;
     }
@@ -1649,7 +1728,7 @@ int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int ba
     (void)hipGraphExecDestroy(h->graphs.front().exec);
     h->graphs.erase(h->graphs.begin());
   }
-  h->graphs.push_back({x, ld_x, N, batch, layer_sq, ld_sq, ws, weights(h, h->L[0]), exec});
+  h->graphs.push_back({x, ld_x, N, batch, layer_sq, ld_sq, ws, score_weights(h), exec});
   return MMAD_OK;
 }
 

@@ -162,8 +162,16 @@ static int check_dims(const char* who, int M, int N, int K, int Mp, int Np, int 
                  Mp, Np, Kp);
   return MMAD_OK;
 }
-static int check_dtype(int dtype) {
-  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16, "bad dtype %d", dtype);
+// x3_ok: the operator has a split-bf16 (MMAD_BF16X3) form; the others refuse
+// that dtype before anything is launched
+static int check_dtype(int dtype, const char* who = "operator", bool x3_ok = false) {
+  if (dtype == MMAD_BF16X3 && !x3_ok) {
+    mmad_set_error("%s: MMAD_BF16X3 covers the eval / score path only (pack, unpack, fc_fwd "
+                   "without stats, fc_fwd_score, deterministic vib_reparam_fwd)", who);
+    return MMAD_EUNSUPPORTED;
+  }
+  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16 || dtype == MMAD_BF16X3, "bad dtype %d",
+                 dtype);
   return MMAD_OK;
 }
 
@@ -207,7 +215,11 @@ static int layer_gemm(int dtype, int epi, const void* A, int lda, const void* B,
 int mmad_fc_fwd(int dtype, int M, int N, int K, int Mp, int Np, int Kp, const void* x,
                 const void* w, const float* bias, int act, float slope, const float* bn_scale,
                 const float* bn_shift, void* y, float* stats, void* stream) {
-  RET_IF(check_dtype(dtype));
+  RET_IF(check_dtype(dtype, "fc_fwd", true));
+  if (dtype == MMAD_BF16X3 && stats) {
+    mmad_set_error("fc_fwd: MMAD_BF16X3 has no BatchNorm statistics epilogue (stats must be NULL)");
+    return MMAD_EUNSUPPORTED;
+  }
   RET_IF(check_dims("fc_fwd", M, N, K, Mp, Np, Kp));
   MMAD_CHECK_ARG(x && w && y, "fc_fwd: null operand");
   MMAD_CHECK_ARG((bn_scale == nullptr) == (bn_shift == nullptr), "fc_fwd: bn_scale/shift pair");
@@ -220,7 +232,7 @@ int mmad_fc_fwd(int dtype, int M, int N, int K, int Mp, int Np, int Kp, const vo
 static int fc_fwd_mse_impl(int dtype, int M, int N, int K, int Mp, int Np, int Kp, const void* x,
                            const void* w, const float* bias, const float* target, int ld_target,
                            int tmod, float grad_scale, void* dz, float* partials, void* stream) {
-  RET_IF(check_dtype(dtype));
+  RET_IF(check_dtype(dtype, "fc_fwd_mse"));
   RET_IF(check_dims("fc_fwd_mse", M, N, K, Mp, Np, Kp));
   MMAD_CHECK_ARG(x && w && dz && target && ld_target >= N, "fc_fwd_mse: bad operands");
   GemmEpi ep{};
@@ -240,7 +252,7 @@ int mmad_fc_fwd_score(int dtype, int M, int N, int K, int Mp, int Np, int Kp, co
                       const void* w, const float* bias, int act, float slope,
                       const float* bn_scale, const float* bn_shift, void* y, const void* ref,
                       float* rowsq, float* diff, int ld_diff, void* stream) {
-  RET_IF(check_dtype(dtype));
+  RET_IF(check_dtype(dtype, "fc_fwd_score", true));
   RET_IF(check_dims("fc_fwd_score", M, N, K, Mp, Np, Kp));
   MMAD_CHECK_ARG(x && w && y && ref && rowsq, "fc_fwd_score: null operand");
   MMAD_CHECK_ARG(!diff || ld_diff >= N, "fc_fwd_score: ld_diff < N");
@@ -254,7 +266,7 @@ int mmad_fc_fwd_score(int dtype, int M, int N, int K, int Mp, int Np, int Kp, co
 int mmad_nap_score(int dtype, int M, int K, int R, int Mp, int Kp, int Rp, const void* x,
                    const void* vt, const float* bias, const float* w, float* rowsq, float* score,
                    void* stream) {
-  RET_IF(check_dtype(dtype));
+  RET_IF(check_dtype(dtype, "nap_score"));
   RET_IF(check_dims("nap_score", M, R, K, Mp, Rp, Kp));
   MMAD_CHECK_ARG(x && vt && bias && w && rowsq && score, "nap_score: null operand");
   GemmEpi ep{};
@@ -266,7 +278,7 @@ int mmad_nap_score(int dtype, int M, int K, int R, int Mp, int Kp, int Rp, const
 
 int mmad_fc_bwd_data(int dtype, int M, int N, int K, int Mp, int Np, int Kp, const void* dz,
                      const void* w, void* dx, float* colsum, void* stream) {
-  RET_IF(check_dtype(dtype));
+  RET_IF(check_dtype(dtype, "fc_bwd_data"));
   RET_IF(check_dims("fc_bwd_data", M, N, K, Mp, Np, Kp));
   MMAD_CHECK_ARG(dz && w && dx, "fc_bwd_data: null operand");
   GemmEpi ep{};
@@ -277,7 +289,7 @@ int mmad_fc_bwd_data(int dtype, int M, int N, int K, int Mp, int Np, int Kp, con
 
 int mmad_fc_bwd_weight(int dtype, int Mp, int Np, int Kp, const void* dz, const void* x,
                        float* dw, void* stream) {
-  RET_IF(check_dtype(dtype));
+  RET_IF(check_dtype(dtype, "fc_bwd_weight"));
   RET_IF(check_dims("fc_bwd_weight", Mp, Np, Kp, Mp, Np, Kp));
   MMAD_CHECK_ARG(dz && x && dw, "fc_bwd_weight: null operand");
   GemmEpi ep{};
@@ -289,7 +301,7 @@ int mmad_fc_bwd_weight(int dtype, int Mp, int Np, int Kp, const void* dz, const 
 int mmad_fc_bwd_weight_adam(int dtype, int Mp, int Np, int Kp, const void* dz, const void* x,
                             float* p, float* m, float* v, void* shadow, float* dw, float beta1,
                             float beta2, float eps, float step_size, float bc2_sqrt, void* stream) {
-  RET_IF(check_dtype(dtype));
+  RET_IF(check_dtype(dtype, "fc_bwd_weight_adam"));
   RET_IF(check_dims("fc_bwd_weight_adam", Mp, Np, Kp, Mp, Np, Kp));
   MMAD_CHECK_ARG(dz && x && p && m && v, "fc_bwd_weight_adam: null operand");
   MMAD_CHECK_ARG(!shadow || dtype == MMAD_BF16, "fc_bwd_weight_adam: the shadow is bf16");

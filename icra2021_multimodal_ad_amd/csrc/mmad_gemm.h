@@ -38,6 +38,15 @@ struct GemmEpi {
   int ldrow;
   float* diff;           // SCORE optional fp32 diff output
   int lddiff;
+  // MMAD_BF16X3 (mmad_gemm_x3.hip) only; ignored by the other dtypes' kernels.
+  // out32 (nullable): an fp32 copy of y, [Mp][ld32].  a_lo / b_lo (nullable):
+  // the operands' lo planes where they do not follow the hi plane at
+  // +rows*ld elements (the executor's weight planes are [2][n_weight]).
+  // out is the hi plane [Mp][ldo], its lo plane follows at +Mp*ldo; ref is fp32.
+  float* out32;
+  int ld32;
+  const void* a_lo;
+  const void* b_lo;
   // FWD/MSE: folded train-mode BN of the producer: bias += sum_p bpart[p][n]
   const float* bpart;    // [bparts][bpstride] (nullable)
   int bparts, bpstride;
@@ -169,6 +178,11 @@ int mmad_gemm_read_status(unsigned* ctl, hipStream_t s, const char* who);
 // column resident; with the whole grid resident, work of other streams can
 // delay it but never block it)
 bool mmad_gemm_bn_fusable(int dtype, int epi, int Mp, int Np);
+
+// the split-bf16 GEMM (MMAD_BF16X3; FWD without statistics and SCORE only),
+// reached through mmad_gemm_dispatch
+int mmad_gemm_x3_dispatch(int epi, const void* A, int lda, const void* B, int ldb, int Mp, int Np,
+                          int K, const GemmEpi& ep, hipStream_t s);
 
 // cfg_used (nullable) receives the tile configuration launched
 int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B, int ldb, int Mp,

@@ -2452,6 +2452,13 @@ int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B
   MMAD_CHECK_ARG(Mp % 128 == 0 && Np % 128 == 0 && K % 128 == 0,
                  "gemm: padded dims must be multiples of 128 (Mp=%d Np=%d K=%d)", Mp, Np, K);
   MMAD_CHECK_ARG(Mp > 0 && Np > 0 && K > 0, "gemm: empty problem");
+  if (dtype == MMAD_BF16X3) {
+    // its own kernel and single tile (mmad_gemm_x3.hip): no plan, no tuning
+    GemmEpi ex = ep_in;
+    ex.dbg = 0;
+    if (cfg_used) *cfg_used = 0;
+    return mmad_gemm_x3_dispatch(epi, A, lda, B, ldb, Mp, Np, K, ex, s);
+  }
   MMAD_CHECK_ARG(dtype == MMAD_BF16 || dtype == MMAD_F32, "gemm: bad dtype %d", dtype);
   GemmEpi ep = ep_in;
   ep.dbg = mmad_dbg_override();

@@ -644,6 +644,77 @@ __global__ void pack_input_k(int M, int K, int Mp, int Kp, const float* __restri
   }
 }
 
+// MMAD_BF16X3 producers: fp32 -> the (hi, lo) bf16 planes
+__device__ __forceinline__ void split_elem(float x, bf16& hi, bf16& lo) {
+  hi = (bf16)x;
+  lo = (bf16)(x - (float)hi);
+}
+
+// 4 values per thread; vec: src 16-byte and hi / lo 8-byte aligned
+__global__ __launch_bounds__(256) void split_planes_k(int64_t n, const float* __restrict__ x,
+                                                      bf16* __restrict__ hi, bf16* __restrict__ lo,
+                                                      int vec) {
+  const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  if (vec && i4 + 4 <= n) {
+    const floatx4 v = *(const floatx4*)(x + i4);
+    bf16x4 h, l;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      bf16 a, b;
+      split_elem(v[k], a, b);
+      h[k] = a;
+      l[k] = b;
+    }
+    *(bf16x4*)(hi + i4) = h;
+    *(bf16x4*)(lo + i4) = l;
+  } else {
+    for (int64_t i = i4; i < n && i < i4 + 4; ++i) split_elem(x[i], hi[i], lo[i]);
+  }
+}
+
+// f32 [M][ldx] -> planes [2][Mp][Kp], 8 values (one 16-byte chunk per plane) per thread
+__global__ __launch_bounds__(256) void pack_planes_k(int M, int K, int Mp, int Kp,
+                                                     const float* __restrict__ x, int ldx, int vec,
+                                                     bf16* __restrict__ out,
+                                                     const MmadDyn* __restrict__ dyn) {
+  if (dyn) x = dyn->x;
+  const int cpr = Kp / 8;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)Mp * cpr) return;
+  const int row = (int)(idx / cpr), c0 = (int)(idx % cpr) * 8;
+  float f[8];
+  if (vec && row < M && c0 + 8 <= K) {
+    const float* src = x + (size_t)row * ldx + c0;
+    const floatx4 a = *(const floatx4*)src, b = *(const floatx4*)(src + 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { f[k] = a[k]; f[4 + k] = b[k]; }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = (row < M && c0 + k < K) ? x[(size_t)row * ldx + c0 + k] : 0.f;
+  }
+  bf16x8 h, l;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    bf16 a, b;
+    split_elem(f[k], a, b);
+    h[k] = a;
+    l[k] = b;
+  }
+  const size_t o = (size_t)row * Kp + c0;
+  *(bf16x8*)(out + o) = h;
+  *(bf16x8*)(out + (size_t)Mp * Kp + o) = l;
+}
+
+__global__ void unpack_planes_k(int M, int N, int Np, const bf16* __restrict__ hi,
+                                const bf16* __restrict__ lo, float* __restrict__ out, int ldo) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)M * N) return;
+  const int row = (int)(idx / N), col = (int)(idx % N);
+  const size_t o = (size_t)row * Np + col;
+  out[(size_t)row * ldo + col] = (float)hi[o] + (float)lo[o];
+}
+
 template <typename T>
 __global__ void unpack_k(int M, int N, int Np, const T* __restrict__ y, float* __restrict__ out,
                          int ldo) {
@@ -907,6 +978,15 @@ __global__ __launch_bounds__(256) void vib_bwd_k(int B, int btl, int k, const T*
 // ===========================================================================
 static inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
+// operators without a split-bf16 form refuse MMAD_BF16X3 before any launch
+#define MMAD_NO_X3(dtype, who)                                                              \
+  do {                                                                                      \
+    if ((dtype) == MMAD_BF16X3) {                                                           \
+      mmad_set_error("%s: MMAD_BF16X3 covers the eval / score path only", who);             \
+      return MMAD_EUNSUPPORTED;                                                             \
+    }                                                                                       \
+  } while (0)
+
 int mmad_bn_eval_affine(int N, int Np, const float* gamma, const float* beta, const float* rm,
                         const float* rv, float eps, float* scale, float* shift, void* stream) {
   MMAD_CHECK_ARG(N >= 0 && Np >= N, "bn_eval_affine: bad sizes");
@@ -921,6 +1001,7 @@ int mmad_bn_train_apply(int dtype, int M, int N, int Mp, int Np, const void* a, 
                         const float* gamma, const float* beta, float* running_mean,
                         float* running_var, float momentum, float eps, float* save_mean,
                         float* save_rstd, void* y, void* stream) {
+  MMAD_NO_X3(dtype, "bn_train_apply");
   MMAD_CHECK_ARG(Mp % 128 == 0 && Np % 128 == 0 && M >= 1 && M <= Mp && N <= Np,
                  "bn_train_apply: bad sizes M=%d Mp=%d N=%d Np=%d", M, Mp, N, Np);
   dim3 grd(Np / SLAB_COLS, Mp / SLAB_ROWS);
@@ -1069,6 +1150,7 @@ int mmad_bn_act_bwd(int dtype, int act, float slope, int M, int N, int Mp, int N
                     const void* a, const float* save_mean, const float* save_rstd,
                     const float* gamma, void* dz, float* dgamma, float* dbeta, float* db_partials,
                     void* ws, void* stream) {
+  MMAD_NO_X3(dtype, "bn_act_bwd");
   MMAD_CHECK_ARG(Mp % 128 == 0 && Np % 128 == 0 && M >= 1 && M <= Mp && N <= Np,
                  "bn_act_bwd: bad sizes");
   dim3 grd(Np / SLAB_COLS, Mp / SLAB_ROWS);
@@ -1134,7 +1216,11 @@ int mmad_pack_input_dyn(int dtype, int M, int K, int Mp, int Kp, const float* x,
   // with dyn the source is read at run time: x is the current call's value
   // (same alignment class is required of every later replay, see mmad_ae)
   const int vec = ((uintptr_t)x % 16 == 0 && ld_x % 4 == 0) ? 1 : 0;
-  if (dtype == MMAD_BF16) {
+  if (dtype == MMAD_BF16X3) {
+    MMAD_CHECK_ARG(Mp % MMAD_PAD == 0 && ((uintptr_t)out % 16) == 0, "pack_input: bad plane buffer");
+    const int64_t n = (int64_t)Mp * (Kp / 8);
+    pack_planes_k<<<nblk(n, 256), 256, 0, s>>>(M, K, Mp, Kp, x, ld_x, vec, (bf16*)out, dyn);
+  } else if (dtype == MMAD_BF16) {
     const int64_t n = (int64_t)Mp * (Kp / 8);
     pack_input_k<bf16, 4><<<nblk(n, 256 * 4), 256, 0, s>>>(M, K, Mp, Kp, x, ld_x, vec, (bf16*)out, dyn);
   } else {
@@ -1156,7 +1242,11 @@ int mmad_unpack_output(int dtype, int M, int N, int Np, const void* y, float* ou
   const int64_t n = (int64_t)M * N;
   if (n == 0) return MMAD_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == MMAD_BF16)
+  if (dtype == MMAD_BF16X3) {
+    const bf16* hi = (const bf16*)y;
+    unpack_planes_k<<<nblk(n, 256), 256, 0, s>>>(M, N, Np, hi, hi + (size_t)mmad_roundup(M, MMAD_PAD) * Np,
+                                                 out, ld_out);
+  } else if (dtype == MMAD_BF16)
     unpack_k<bf16><<<nblk(n, 256), 256, 0, s>>>(M, N, Np, (const bf16*)y, out, ld_out);
   else
     unpack_k<float><<<nblk(n, 256), 256, 0, s>>>(M, N, Np, (const float*)y, out, ld_out);
@@ -1241,6 +1331,16 @@ int mmad_to_bf16(int64_t n, const float* x, void* y, void* stream) {
   return MMAD_OK;
 }
 
+int mmad_split_planes(int64_t n, const float* src, void* hi, void* lo, void* stream) {
+  MMAD_CHECK_ARG(n >= 0 && (n == 0 || (src && hi && lo)), "split_planes: bad arguments");
+  if (n == 0) return MMAD_OK;
+  const int vec = ((uintptr_t)src % 16 == 0 && (uintptr_t)hi % 8 == 0 && (uintptr_t)lo % 8 == 0) ? 1 : 0;
+  split_planes_k<<<nblk((n + 3) / 4, 256), 256, 0, (hipStream_t)stream>>>(n, src, (bf16*)hi, (bf16*)lo,
+                                                                         vec);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
 int mmad_from_bf16(int64_t n, const void* x, float* y, void* stream) {
   if (n == 0) return MMAD_OK;
   from_bf16_k<<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(n, (const bf16*)x, y);
@@ -1264,7 +1364,19 @@ int mmad_vib_reparam_fwd_dyn(int dtype, int B, int btl, int k, const void* enc_o
   const int Mpz = mmad_roundup(k * B, MMAD_PAD);
   const int64_t n = (int64_t)Mpz * ld_z;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == MMAD_BF16)
+  if (dtype == MMAD_BF16X3) {
+    if (!deterministic || kl_partial) {
+      mmad_set_error("vib_reparam_fwd: MMAD_BF16X3 is deterministic only (z = mu, no KL partials)");
+      return MMAD_EUNSUPPORTED;
+    }
+    // z = mu: the same copy on each plane
+    const bf16* e = (const bf16*)enc_out;
+    bf16* zz = (bf16*)z;
+    const size_t eo = (size_t)mmad_roundup(B, MMAD_PAD) * ld_enc, zo = (size_t)Mpz * ld_z;
+    for (int p = 0; p < 2; ++p)
+      vib_fwd_k<bf16><<<nblk(n, 256), 256, 0, s>>>(B, btl, k, e + p * eo, ld_enc, nullptr, nullptr, 0, 0,
+                                                   1, zz + p * zo, ld_z, Mpz, nullptr, nullptr);
+  } else if (dtype == MMAD_BF16)
     vib_fwd_k<bf16><<<nblk(n, 256), 256, 0, s>>>(B, btl, k, (const bf16*)enc_out, ld_enc, eps,
                                                  eps_out, seed, offset, deterministic, (bf16*)z,
                                                  ld_z, Mpz, kl_partial, dyn);
@@ -1284,6 +1396,7 @@ int64_t mmad_vib_kl_parts(int B, int k, int ld_z) {
 int mmad_vib_reparam_bwd(int dtype, int B, int btl, int k, const void* enc_out, int ld_enc,
                          const float* eps, const void* dz, int ld_dz, float beta_kl,
                          void* d_enc_out, int ld_denc, float* colsum, void* stream) {
+  MMAD_NO_X3(dtype, "vib_reparam_bwd");
   MMAD_CHECK_ARG(B >= 1 && btl >= 1 && k >= 1 && ld_denc >= 2 * btl, "vib_reparam_bwd: bad sizes");
   const int Mpe = mmad_roundup(B, MMAD_PAD);
   const int64_t n = (int64_t)Mpe * ld_denc;
@@ -1303,6 +1416,7 @@ int mmad_vib_reparam_bwd(int dtype, int B, int btl, int k, const void* enc_out, 
 
 int mmad_act_bwd(int dtype, int act, float slope, int M, int Mp, int Np, const void* dy,
                  const void* a, void* dz, float* db_partials, void* stream) {
+  MMAD_NO_X3(dtype, "act_bwd");
   MMAD_CHECK_ARG(Mp % 128 == 0 && Np % 128 == 0 && M >= 0 && M <= Mp && dy && a && dz && db_partials,
                  "act_bwd: bad arguments");
   dim3 grd(Np / SLAB_COLS, Mp / SLAB_ROWS);

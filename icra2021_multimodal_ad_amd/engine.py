@@ -56,6 +56,8 @@ class NativeAE:
         self._alloc(device)
         self._ws = None
         self._synced_version = None
+        self._score_precision = None   # set_score_precision: None or "bf16x3"
+        self._planes = None
         # version of the fp32 master as the plugin surface sees it: the
         # reference-shaped nn.Parameters are views with their OWN version
         # counters (load_state_dict / a torch optimizer bump those, not
@@ -98,6 +100,11 @@ class NativeAE:
              ptr(self.running))
         if self._pair:
             call("mmad_ae_set_shadow_pair", self._h, ptr(sb[self.n_weight:]))
+        if getattr(self, "_score_precision", None) is not None:
+            # the score planes follow the buffers (a rebind, a new device)
+            if self._planes is None or self._planes.device != self.device:
+                self._planes = torch.zeros(2 * self.n_weight, device=self.device, dtype=torch.bfloat16)
+            call("mmad_ae_set_score_planes", self._h, ptr(self._planes))
         if getattr(self, "_grad_bf16", None) is not None:
             # the bf16 exchange scratch follows the buffers to their new device
             self.set_grad_bf16(True)
@@ -123,6 +130,31 @@ class NativeAE:
         self._ws = None
         self._dw_streams = None   # the torch exchange's bucket streams belong to the old device
         return self
+
+    def set_score_precision(self, precision):
+        """``"bf16x3"``: an fp32 model's eval forward / validate / score passes
+        run their GEMMs on the bf16 matrix cores over split-bf16 weight planes
+        (mmad_ae_set_score_planes; this object owns the 2*n_weight bf16
+        buffer); training is untouched.  ``None`` detaches."""
+        if precision not in (None, "bf16x3"):
+            raise ValueError(f"score precision {precision!r}: expected 'bf16x3' or None")
+        if precision is not None and self.dt != _native.F32:
+            raise ValueError("score precision 'bf16x3' is for fp32 models (a bf16 model scores on "
+                             "its own shadow)")
+        self._score_precision = precision
+        self._synced_version = None
+        self._ws = None            # the workspace size depends on it
+        if precision is None:
+            self._planes = None
+            if self.device.type == "cuda":
+                call("mmad_ae_set_score_planes", self._h, None)
+        elif self.device.type == "cuda":
+            self._bind()
+
+    @property
+    def score_dtype(self):
+        """MMAD dtype of the eval / score GEMMs (F32, BF16 or BF16X3)."""
+        return int(self._lib.mmad_ae_score_dtype(self._h))
 
     def set_comm(self, comm):
         """Attach a dist.NativeComm (or None): mmad_ae_train_step then exchanges
@@ -200,8 +232,9 @@ class NativeAE:
 
     def sync_shadow(self, force=False):
         """Refresh the bf16 weight shadow if the fp32 master was written by
-        anything other than the native Adam (load_state_dict, torch optim)."""
-        if self.shadow is None or self.device.type != "cuda":
+        anything other than the native Adam (load_state_dict, torch optim);
+        for an fp32 model with score planes attached, the planes."""
+        if (self.shadow is None and self._planes is None) or self.device.type != "cuda":
             return
         v = self.master_version()
         if force or v != self._synced_version:
@@ -210,7 +243,7 @@ class NativeAE:
 
     def _mark_synced(self):
         """The native Adam just wrote the master AND the shadow."""
-        if self.shadow is not None:
+        if self.shadow is not None or self._planes is not None:
             self._synced_version = self.master_version()
 
     def check_status(self):

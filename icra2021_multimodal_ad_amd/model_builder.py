@@ -4,7 +4,9 @@ Same config fields (input_size int or (C,H,W), btl_size, n_layers, gpu_id);
 ``config.models`` (parsed but ignored by the reference, model_builder.py:48-49)
 selects 'ae' or 'vib_ae' here.  Build extras, all optional: ``dtype``
 ('f32' default = reference numerics, 'bf16' = throughput path), ``vib_k``,
-``beta_kl``.
+``beta_kl``, ``score_dtype`` ('bf16x3': an fp32 model scores on the bf16 matrix
+cores over split-bf16 planes; absent = the model's own dtype; ignored with a
+warning for dtype='bf16').
 """
 from .auto_encoder import AutoEncoder
 from .common_utils import get_hidden_layer_sizes, flatten_input_size
@@ -41,6 +43,7 @@ def ae_wrapper(config):
         vib=vib,
         k=getattr(config, "vib_k", 1),
         beta_kl=getattr(config, "beta_kl", 1.0),
+        score_dtype=getattr(config, "score_dtype", None),
     )
 
 

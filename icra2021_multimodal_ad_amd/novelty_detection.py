@@ -60,7 +60,9 @@ def _nap_model(model, cfg):
     (profiles/r03v_e2e_bf16_training.json).  For a bf16 model NAP therefore
     reads the diffs of an fp32 eval twin built from the same fp32 master
     weights and BN statistics (the reference's own precision); BASE / SAP stay
-    on the bf16 path.  ``config.nap_dtype = 'model'`` keeps the model's own."""
+    on the bf16 path.  ``config.nap_dtype = 'model'`` keeps the model's own.
+    The twin is built from a copy of the config, so it inherits
+    ``config.score_dtype`` ('bf16x3': its diffs come from the split-bf16 GEMMs)."""
     if getattr(model, "mmad_dtype", "f32") == "f32" or getattr(cfg, "nap_dtype", "f32") != "f32":
         return model
     import types

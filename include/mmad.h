@@ -16,8 +16,18 @@
  *    "Mp/Np/Kp" the padded ones.
  *  - dtype selects the activation/weight storage type of the GEMM operands
  *    (MMAD_F32: exact-fp32 parity path on f32 MFMA; MMAD_BF16: bf16 storage,
- *    fp32 accumulation).  Gradients, optimizer state, BN statistics and all
+ *    fp32 accumulation; MMAD_BF16X3: split-bf16 planes, eval / score path
+ *    only, see below).  Gradients, optimizer state, BN statistics and all
  *    reductions are fp32.
+ *  - MMAD_BF16X3 ("x3"): a packed [Mp][ld] matrix is two bf16 planes in one
+ *    allocation of fp32's size -- hi [Mp][ld], then lo at +Mp*ld elements --
+ *    with hi = RNE_bf16(x), lo = RNE_bf16(x - float(hi)), zero padding in both;
+ *    it stands for float(hi) + float(lo).  GEMMs form hi.hi + (hi.lo + lo.hi)
+ *    on the bf16 matrix cores with fp32 accumulation (fp32-class results at
+ *    three bf16 MFMAs per step).  Accepted by mmad_pack_input,
+ *    mmad_unpack_output, mmad_fc_fwd (stats == NULL), mmad_fc_fwd_score and
+ *    mmad_vib_reparam_fwd (deterministic); every other operator returns
+ *    MMAD_EUNSUPPORTED for it and launches nothing.
  *  - Every call returns 0 (MMAD_OK) or a negative status; the message is in
  *    mmad_last_error_string() (thread-local).  No exceptions cross the ABI.
  *  - stream is a hipStream_t passed as void* (0 = legacy default stream).
@@ -35,7 +45,7 @@ extern "C" {
 #define MMAD_ABI_VERSION 1
 
 enum { MMAD_OK = 0, MMAD_EINVAL = -1, MMAD_EUNSUPPORTED = -2, MMAD_EHIP = -3, MMAD_ERCCL = -4 };
-enum { MMAD_F32 = 0, MMAD_BF16 = 1 };
+enum { MMAD_F32 = 0, MMAD_BF16 = 1, MMAD_BF16X3 = 2 };
 /* modules/activation.py:20-45 (names 'leakyrelu', 'relu', 'sigmoid', 'tanh', None) */
 enum { MMAD_ACT_NONE = 0, MMAD_ACT_LEAKYRELU = 1, MMAD_ACT_RELU = 2, MMAD_ACT_SIGMOID = 3,
        MMAD_ACT_TANH = 4, MMAD_ACT_LOGSIGMOID = 5, MMAD_ACT_SOFTMAX = 6, MMAD_ACT_LOGSOFTMAX = 7 };
@@ -146,7 +156,8 @@ int mmad_gemm_status(void* stream);
  * bn_scale/bn_shift (nullable): eval-mode BatchNorm1d as a per-column affine
  * (see mmad_bn_eval_affine).  stats (nullable, fp32 [Mp/32][2][Np]): per
  * 32-row chunk Welford (mean, M2) of the post-activation values, consumed by
- * mmad_bn_train_apply for train-mode BN.  Rows >= M and cols >= N are written 0. */
+ * mmad_bn_train_apply for train-mode BN.  Rows >= M and cols >= N are written 0.
+ * MMAD_BF16X3: stats must be NULL (MMAD_EUNSUPPORTED otherwise). */
 int mmad_fc_fwd(int dtype, int M, int N, int K, int Mp, int Np, int Kp, const void* x,
                 const void* w, const float* bias, int act, float slope, const float* bn_scale,
                 const float* bn_shift, void* y, float* stats, void* stream);
@@ -162,7 +173,10 @@ int mmad_fc_fwd_mse(int dtype, int M, int N, int K, int Mp, int Np, int Kp, cons
 /* Eval-mode FCLayer.forward fused with the per-window squared-diff reduction
  * of reconstruction_aggregation.py:22-28: y as mmad_fc_fwd (eval affine), and
  * rowsq[Np/128][Mp] = per-128-column partial sums of (y - ref)^2; diff
- * (nullable, fp32, ld_diff) receives y - ref for the valid region. */
+ * (nullable, fp32, ld_diff) receives y - ref for the valid region.
+ * MMAD_BF16X3: ref is FP32 [Mp][Np] (not planes) and is subtracted from the
+ * fp32 value of y before y is rounded to its planes, so the diff carries the
+ * GEMM's precision, not the storage's; only its valid region is read. */
 int mmad_fc_fwd_score(int dtype, int M, int N, int K, int Mp, int Np, int Kp, const void* x,
                       const void* w, const float* bias, int act, float slope,
                       const float* bn_scale, const float* bn_shift, void* y, const void* ref,
@@ -273,11 +287,16 @@ int mmad_mse_loss(int64_t n, const float* y_hat, const float* y, int mean, float
 int mmad_mse_grad(int64_t n, const float* y_hat, const float* y, const float* g, int mean, float* d_yhat,
                   float* d_y, void* stream);
 
-/* f32 [M][ld_x] -> packed dtype [Mp][Kp] (zero padding). */
+/* Elementwise split of n fp32 values into the two bf16 planes of MMAD_BF16X3:
+ * hi[i] = RNE_bf16(src[i]), lo[i] = RNE_bf16(src[i] - float(hi[i])). */
+int mmad_split_planes(int64_t n, const float* src, void* hi, void* lo, void* stream);
+
+/* f32 [M][ld_x] -> packed dtype [Mp][Kp] (zero padding; MMAD_BF16X3: both planes). */
 int mmad_pack_input(int dtype, int M, int K, int Mp, int Kp, const float* x, int ld_x, void* out,
                     void* stream);
 
-/* packed dtype [Mp][Np] -> f32 [M][ld_out] (valid region). */
+/* packed dtype [Mp][Np] -> f32 [M][ld_out] (valid region).  MMAD_BF16X3:
+ * hi + lo, with Mp = M rounded up to the pad granule (the lo plane's offset). */
 int mmad_unpack_output(int dtype, int M, int N, int Np, const void* y, float* out, int ld_out,
                        void* stream);
 
@@ -301,7 +320,10 @@ int mmad_adam(int64_t n, float* p, const float* g, float* m, float* v, float bet
  * (nullable -> Philox N(0,1) from seed/offset; the draw is stored to eps_out,
  * nullable).  deterministic != 0 -> z = mu (no_grad and not stochastic).
  * kl_partial (nullable): fp32 [Mp/128] partial sums of
- * -0.5*(1 + lv - mu^2 - exp(lv)) (build-defined KL, SURVEY §8 a10'). */
+ * -0.5*(1 + lv - mu^2 - exp(lv)) (build-defined KL, SURVEY §8 a10').
+ * MMAD_BF16X3: only deterministic != 0 with kl_partial == NULL (z = mu, a
+ * copy of both planes; B rounded up to the granule locates enc_out's lo
+ * plane); MMAD_EUNSUPPORTED otherwise. */
 int mmad_vib_reparam_fwd(int dtype, int B, int btl, int k, const void* enc_out, int ld_enc,
                          const float* eps, float* eps_out, uint64_t seed, uint64_t offset,
                          int deterministic, void* z, int ld_z, float* kl_partial, void* stream);
@@ -344,8 +366,28 @@ int mmad_ae_bind(mmad_ae* h, float* params, float* grads, float* adam_m, float* 
                  void* shadow, float* running /* [2][n_bn]: mean then var */);
 
 /* Refresh the bf16 weight shadow from the fp32 params (after a host-side
- * load_state_dict or any external parameter write).  No-op for MMAD_F32. */
+ * load_state_dict or any external parameter write).  MMAD_F32: refreshes the
+ * score planes if attached (mmad_ae_set_score_planes), otherwise a no-op. */
 int mmad_ae_sync_shadow(mmad_ae* h, void* stream);
+
+/* Split-bf16 scoring for an MMAD_F32 handle.  planes: bf16 [2][n_weight] (hi
+ * then lo), caller-owned; NULL detaches.  With planes attached,
+ * mmad_ae_forward(train_bn = 0), mmad_ae_score and mmad_ae_score_stream run
+ * their GEMMs as MMAD_BF16X3 (activations as planes, per-layer references and
+ * diffs in fp32); everything else on the handle -- train_bn = 1 forwards,
+ * every training entry point, Adam -- runs exactly as without them.  The
+ * handle keeps the planes fresh: mmad_ae_bind, this call and every entry point
+ * that writes weights mark them stale, and the three scoring entry points
+ * re-split the weight region (one mmad_split_planes launch on the caller's
+ * stream, outside any graph replay) when they are.  External parameter writes
+ * (load_state_dict) follow the bf16 shadow's contract: call
+ * mmad_ae_sync_shadow, which refreshes the planes of an F32 handle.
+ * mmad_ae_workspace_bytes grows (fp32 reference copies, carved after every
+ * other buffer) while planes are attached; attaching or detaching drops the
+ * cached score graphs.  MMAD_EINVAL on a bf16 handle. */
+int mmad_ae_set_score_planes(mmad_ae* h, void* planes);
+/* dtype of the eval / score GEMMs: MMAD_F32, MMAD_BF16 or MMAD_BF16X3 (-1: null handle) */
+int mmad_ae_score_dtype(const mmad_ae* h);
 
 /* bf16 only: a second n_weight-element bf16 buffer (NULL turns it off).  The
  * fused step (mmad_ae_train_step) then writes the updated weights into the
