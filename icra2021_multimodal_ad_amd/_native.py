@@ -31,6 +31,7 @@ SIGNATURES = {
     "mmad_tune_set": (_I, [_I, _I]),
     "mmad_tune_get": (_I, [_I, ctypes.POINTER(_I)]),
     "mmad_gemm_splitk_for": (_I, [_I, _I, _I, _I, _I]),
+    "mmad_gemm_tile_for": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "mmad_gemm_ws_bytes": (ctypes.c_size_t, []),
     "mmad_gemm_set_workspace": (_I, [_P, ctypes.c_size_t]),
     "mmad_gemm_status": (_I, [_P]),

@@ -146,6 +146,11 @@ int mmad_gemm_splitk_for(int Mp, int Np, int K, int dtype, int epi) {
   if (Mp <= 0 || Np <= 0 || K <= 0 || epi < 0 || epi > 4) return 1;
   return mmad_gemm_splitk(Mp, Np, K, dtype, epi);
 }
+int mmad_gemm_tile_for(int forced_cfg, int dtype, int epi, int Mp, int Np, int splitk, int fused_bn,
+                       int has_partials, int act) {
+  return mmad_gemm_tile(forced_cfg, GemmProblem{dtype, epi, Mp, Np, splitk, fused_bn != 0,
+                                                has_partials != 0, act});
+}
 
 #define RET_IF(x)              \
   do {                         \

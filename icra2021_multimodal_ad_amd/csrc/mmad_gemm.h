@@ -1,6 +1,9 @@
 // Internal GEMM interface (not part of the C-ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+
+#include "mmad_common.h"
 
 // split-K control block: per-launch arrival counters + flags use fewer than
 // MMAD_SK_ERR_WORD words (mmad_gemm_splitk checks); this word records a combine that timed out (sticky until read
@@ -150,6 +153,36 @@ int mmad_tile_adam_for(int Mp, int Np, int K);   // ... for a shape
 int mmad_tile_adam_main_override();  // >= 0: ... of those on the main stream
 int mmad_tile_adam_main_for(int Mp, int Np, int K);   // ... for a shape (-2: rule)
 int mmad_tile_epi_override(int epi);  // >= 0: tile of this epilogue's GEMMs
+
+// A GEMM as the dispatcher sees it when it picks a tile: everything the rule
+// for "which kernel runs" depends on (mmad_gemm_mfma.hip: tile_allowed,
+// tile_runs), and nothing else.
+struct GemmProblem {
+  int dtype, epi;   // MMAD_F32 / MMAD_BF16, GemmEpiKind
+  int Mp, Np;       // padded output shape
+  int splitk;       // split factor (1 = none)
+  bool fused_bn;    // train-mode BN fused into the launch (GemmEpi::bn_sync)
+  bool partials;    // column partials read or written (GemmEpi::part / bpart)
+  int act;          // MMAD_ACT_*
+};
+// the tile whose kernel runs when `cfg` is chosen for `p` (a register-direct
+// tile outside its epilogue runs as its row-quad twin), or -1 when `cfg` may
+// not be chosen for it.  Pure: no device, no knob.
+int mmad_gemm_tile(int cfg, const GemmProblem& p);
+
+// The launch of every GEMM kernel here: `args` holds one pointer per kernel
+// parameter.  The events (nullable) ride on the launch itself through the
+// extended entry point; a launch without them takes the plain one (the one
+// `<<<>>>` ends in), so captured graphs hold the same node either way.
+inline int mmad_gemm_launch(const void* fn, dim3 grid, dim3 block, hipStream_t s, hipEvent_t start_ev,
+                            hipEvent_t done_ev, void** args) {
+  if (start_ev || done_ev)
+    (void)hipExtLaunchKernel(fn, grid, block, args, 0, s, start_ev, done_ev, 0);
+  else
+    (void)hipLaunchKernel(fn, grid, block, args, 0, s);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
 
 // tile configuration a problem will run with (autotuned on first dispatch of
 // the shape; a static heuristic before that / when tuning is off)

@@ -22,7 +22,12 @@
 // tiles give the narrow layers enough blocks.  Which one a shape gets is
 // measured on first use (mmad_gemm_dispatch autotune): the accumulation
 // order over K is the same for every tile, so the choice never changes a
-// result bit.
+// result bit.  Tiles 6-9 (256x256 and the register-direct forms) are
+// described at their Cfg<N>.  Which tiles may run a problem, which tile then
+// runs and which instantiation that is, is decided in one block of the host
+// part below the kernels: the tile table TILES, the rule tile_allowed /
+// tile_runs over a GemmProblem, and kernel_of generated from the table.  A
+// new tile is entered once: its Cfg<N> and its row of TILES.
 // K stage = 128 bytes of K per operand row (BK = 64 bf16 / 32 f32), staged
 // global -> LDS by global_load_lds (16 B/lane, no registers), NS-stage ring
 // with a counted vmcnt and a raw s_barrier so NS-2 stages stay in flight
@@ -86,7 +91,7 @@ template <> struct Cfg<7> { static constexpr int BM = 256, BN = 256, WM = 2, WN 
 // than the 8-wave 128x64 wave tiles.  Compiled in its own translation unit
 // (this file with MMAD_GEMM_B4_TU, csrc/Makefile) WITHOUT the VGPR-form MFMA
 // flag the other tiles use: 256 + ~150 registers need the AGPR half of the
-// file; the host side reaches it through mmad_gemm_b4_launch.
+// file; the host side reaches it through mmad_gemm_b4_kernel.
 constexpr int CFG_B4 = 8;
 template <> struct Cfg<8> { static constexpr int BM = 256, BN = 256, WM = 2, WN = 2, NS = 2, NT = 256; };
 // 9: CFG 1 (256x128, 8 waves of 64x64) with CFG 7's swapped operands and
@@ -95,33 +100,16 @@ template <> struct Cfg<8> { static constexpr int BM = 256, BN = 256, WM = 2, WN 
 constexpr int CFG_XST1 = 9;
 template <> struct Cfg<9> { static constexpr int BM = 256, BN = 128, WM = 4, WN = 2, NS = 3, NT = 512; };
 constexpr int NCFG = 10;
-// capacity-cache keys pack (device, dtype, epilogue, cfg) into one integer
-// with 8 slots per epilogue field and 16 per cfg field
-static_assert(NCFG <= 16, "widen the cfg field of the capacity-cache keys");
-constexpr int CFG_BM[NCFG] = {128, 256, 128, 64, 64, 128, 256, 256, 256, 256};
-constexpr int CFG_BN[NCFG] = {128, 128, 256, 64, 128, 128, 256, 256, 256, 128};
-constexpr int CFG_NT[NCFG] = {512, 512, 512, 256, 256, 256, 512, 512, 256, 512};
-inline bool is_big(int cfg) { return cfg == CFG_BIG || cfg == CFG_XST || cfg == CFG_B4; }
-inline bool is_xst(int cfg) { return cfg == CFG_XST || cfg == CFG_B4 || cfg == CFG_XST1; }
-// the row-quad tile a register-direct one falls back to (same tile shape)
-inline int xst_base(int cfg) { return cfg == CFG_XST1 ? 1 : CFG_BIG; }
-// the 256x256 tiles: bf16 operands, forward-type epilogues, no fused BN
+// which (operand type, epilogue) pairs the 256x256 tiles (6, 7, 8) and the
+// register-direct tiles (7, 8, 9) are instantiated for; the host-side tile
+// table and tile_allowed (below the kernels) state the same per problem
 template <typename T, int EPI>
 constexpr bool big_ok() {
   return sizeof(T) == 2 && (EPI == GEMM_EPI_FWD || EPI == GEMM_EPI_MSE || EPI == GEMM_EPI_SCORE);
 }
-inline bool big_ok_rt(int dtype, int epi) {
-  return dtype == MMAD_BF16 && (epi == GEMM_EPI_FWD || epi == GEMM_EPI_MSE || epi == GEMM_EPI_SCORE);
-}
-// the register-direct 256x256 tile: eval forward / score, piecewise-linear
-// activations (act_is_linear_piecewise: declared in mmad_common.h)
 template <typename T, int EPI>
 constexpr bool xst_ok() {
   return sizeof(T) == 2 && (EPI == GEMM_EPI_FWD || EPI == GEMM_EPI_SCORE);
-}
-inline bool xst_ok_rt(int dtype, int epi, const GemmEpi& ep) {
-  return dtype == MMAD_BF16 && (epi == GEMM_EPI_FWD || epi == GEMM_EPI_SCORE) && !ep.part && !ep.bpart &&
-         act_is_linear_piecewise(ep.act);
 }
 
 template <typename T, bool KMAJ, int ROWS, int NT>
@@ -1004,7 +992,7 @@ __device__ __forceinline__ void gemm_body(const T* __restrict__ A, int lda, cons
     // 2h and 2h+1 are stored together: v_permlane16_swap of their quads gives
     // lane g the 8 columns 8(g>>1) .. +7 of tile 2h + (g&1) (16 B).
     // (piecewise-linear activations only: LeakyReLU / ReLU / none; sigmoid /
-    // tanh layers run on CFG 6, xst_ok_rt)
+    // tanh layers run on CFG 6, tile_runs)
     const bool pw_relu = ep.act == MMAD_ACT_RELU;
     const float pw_lo = act_lo_slope(ep.act, ep.slope);
     auto cvec = [&](const float* p, int col, float dflt) -> floatx4 {
@@ -1995,49 +1983,102 @@ __global__ __launch_bounds__(Cfg<CFG>::NT, 1) void mmad_gemm_kernel_p(const T* _
 }
 
 #ifdef MMAD_GEMM_B4_TU
-// ---- the 4-wave 256x256 translation unit: its launcher only --------------
-int mmad_gemm_b4_launch(int epi, const void* A, int lda, const void* B, int ldb, int Mp, int Np, int K,
-                        const GemmEpi& ep, hipStream_t s) {
-  dim3 grd((Mp / 256) * (Np / 256)), blk(256);
-  auto go = [&](auto kern) {
-    if (ep.done_ev || ep.start_ev)
-      hipExtLaunchKernelGGL(kern, grd, blk, 0u, s, ep.start_ev, ep.done_ev, 0u, (const bf16*)A, lda,
-                            (const bf16*)B, ldb, K, ep);
-    else
-      kern<<<grd, blk, 0, s>>>((const bf16*)A, lda, (const bf16*)B, ldb, K, ep);
-  };
-  if (epi == GEMM_EPI_FWD) go(mmad_gemm_kernel<bf16, bf16, true, true, CFG_B4, GEMM_EPI_FWD>);
-  else if (epi == GEMM_EPI_SCORE) go(mmad_gemm_kernel<bf16, bf16, true, true, CFG_B4, GEMM_EPI_SCORE>);
-  else {
-    mmad_set_error("gemm: tile 8 runs the eval forward / score epilogues only");
-    return MMAD_EUNSUPPORTED;
-  }
-  MMAD_LAUNCH_CHECK();
-  return MMAD_OK;
+// ---- the 4-wave 256x256 translation unit: tile 8's two kernels only --------
+const void* mmad_gemm_b4_kernel(int epi) {
+  if (epi == GEMM_EPI_FWD) return (const void*)mmad_gemm_kernel<bf16, bf16, true, true, CFG_B4, GEMM_EPI_FWD>;
+  if (epi == GEMM_EPI_SCORE) return (const void*)mmad_gemm_kernel<bf16, bf16, true, true, CFG_B4, GEMM_EPI_SCORE>;
+  return nullptr;
 }
 #else
-int mmad_gemm_b4_launch(int epi, const void* A, int lda, const void* B, int ldb, int Mp, int Np, int K,
-                        const GemmEpi& ep, hipStream_t s);
+const void* mmad_gemm_b4_kernel(int epi);
 
 // -------------------------------------------------------------------------
 // host-side planning and launch
+//
+// "Which kernel runs for this problem" is answered here and nowhere else:
+//   TILES        what a tile is: its numbers (from Cfg<N>) and its kind;
+//   tile_allowed / tile_runs
+//                which tiles may be chosen for a GemmProblem, and the tile
+//                whose kernel then runs (a register-direct tile outside its
+//                epilogue runs as its row-quad base: same shape, same bits);
+//   kernel_of    (tile, persistent) -> kernel instantiation, from TILES.
+// The dispatcher, the tuner, the planners and the launch path only read
+// these.  A new tile of an existing kind is entered in ONE place: its row of
+// TILES (next to its Cfg<N> and NCFG); a new kind adds its flag and its
+// clause in tile_allowed.
 // -------------------------------------------------------------------------
-static bool cfg_fits(int cfg, int Mp, int Np, int epi, int dtype) {
-  if (Mp % CFG_BM[cfg] || Np % CFG_BN[cfg]) return false;
-  if (is_big(cfg) && !big_ok_rt(dtype, epi)) return false;
-  if (is_xst(cfg) && !(dtype == MMAD_BF16 && (epi == GEMM_EPI_FWD || epi == GEMM_EPI_SCORE))) return false;
+struct Tile {
+  int BM, BN, NT;
+  bool big;       // a 256x256 tile
+  bool xst;       // stores register-direct (MFMA operands swapped)
+  int base;       // the row-quad tile of the same shape (itself unless xst)
+  bool persist;   // has a persistent form (mmad_gemm_kernel_p, knob 12)
+};
+template <int C>
+constexpr Tile tile(bool big = false, bool xst = false, int base = C, bool persist = false) {
+  return {Cfg<C>::BM, Cfg<C>::BN, Cfg<C>::NT, big, xst, base, persist};
+}
+constexpr Tile TILES[NCFG] = {
+    tile<0>(),
+    tile<1>(false, false, 1, true),
+    tile<2>(false, false, 2, true),
+    tile<3>(),
+    tile<4>(),
+    tile<5>(),
+    tile<CFG_BIG>(true, false, CFG_BIG, true),
+    tile<CFG_XST>(true, true, CFG_BIG, true),
+    tile<CFG_B4>(true, true, CFG_BIG),
+    tile<CFG_XST1>(false, true, 1),
+};
+// callers size buffers from the tile that runs (the MSE loss partials), and
+// the fallback is meant to change no bit: a base keeps its tile's shape
+constexpr bool bases_keep_shape() {
+  for (int c = 0; c < NCFG; ++c) {
+    const Tile &t = TILES[c], &b = TILES[t.base];
+    if (b.BM != t.BM || b.BN != t.BN || b.xst || (!t.xst && t.base != c)) return false;
+  }
+  return true;
+}
+static_assert(bases_keep_shape(), "a tile's row-quad base must have its shape");
+
+// may `cfg` be chosen for `p`?  (Co-residency of a fused-BN grid is a device
+// query the callers apply on top.)
+static bool tile_allowed(int cfg, const GemmProblem& p) {
+  if (cfg < 0 || cfg >= NCFG) return false;
+  const Tile& t = TILES[cfg];
+  const int e = p.epi;
+  if (p.dtype != MMAD_BF16 && p.dtype != MMAD_F32) return false;
+  if (e < GEMM_EPI_FWD || e > GEMM_EPI_SCORE) return false;
+  if (p.Mp <= 0 || p.Np <= 0 || p.Mp % t.BM || p.Np % t.BN) return false;
+  // 256x256: bf16 forward-type epilogues; register-direct: eval forward / score
+  const bool bf16_in = p.dtype == MMAD_BF16;
+  if (t.big && !(bf16_in && (e == GEMM_EPI_FWD || e == GEMM_EPI_MSE || e == GEMM_EPI_SCORE))) return false;
+  if (t.xst && !(bf16_in && (e == GEMM_EPI_FWD || e == GEMM_EPI_SCORE))) return false;
   // the score epilogue reduces rows over 128-column groups inside one tile
-  if (epi == GEMM_EPI_SCORE && CFG_BN[cfg] < 128) return false;
+  if (e == GEMM_EPI_SCORE && t.BN < 128) return false;
+  // neither kind combines split-K slices or joins the fused-BN column barrier
+  if ((t.big || t.xst) && (p.splitk > 1 || p.fused_bn)) return false;
+  if (p.fused_bn && e != GEMM_EPI_FWD && e != GEMM_EPI_BWD_DATA) return false;
   return true;
 }
 
-int mmad_gemm_ntiles(int cfg, int Mp, int Np) { return (Mp / CFG_BM[cfg]) * (Np / CFG_BN[cfg]); }
+// the tile whose kernel is launched when an allowed `cfg` is chosen: the
+// register-direct epilogue has no column partials (the BN statistics need the
+// row-quad layout) and piecewise-linear activations only
+static int tile_runs(int cfg, const GemmProblem& p) {
+  const Tile& t = TILES[cfg];
+  return t.xst && (p.partials || !act_is_linear_piecewise(p.act)) ? t.base : cfg;
+}
+
+int mmad_gemm_tile(int cfg, const GemmProblem& p) { return tile_allowed(cfg, p) ? tile_runs(cfg, p) : -1; }
+
+int mmad_gemm_ntiles(int cfg, int Mp, int Np) { return (Mp / TILES[cfg].BM) * (Np / TILES[cfg].BN); }
 
 int mmad_gemm_tiles(int Mp, int Np) { return (Mp / 64) * (Np / 64); }
 
 // static choice when autotuning is off or impossible (stream capture)
 template <typename Pred>
-static int heuristic_cfg(int Mp, int Np, int epi, Pred allowed) {
+static int heuristic_cfg(int Mp, int Np, Pred allowed) {
   const int order[] = {CFG_BIG, 1, 0, 5, 4, 3};
   const int want[] = {512, 200, 200, 200, 160, 0};
   for (int i = 0; i < 6; ++i) {
@@ -2047,11 +2088,7 @@ static int heuristic_cfg(int Mp, int Np, int epi, Pred allowed) {
   }
   for (int c : {4, 0, 3, 5, 2, 1})
     if (allowed(c)) return c;
-  (void)Mp; (void)Np; (void)epi;
   return -1;
-}
-static int heuristic_cfg(int Mp, int Np, int epi, int dtype) {
-  return heuristic_cfg(Mp, Np, epi, [&](int c) { return cfg_fits(c, Mp, Np, epi, dtype); });
 }
 
 // group height balancing the per-XCD A-panel (gm*BM rows) and B-panel
@@ -2064,237 +2101,120 @@ static int plan_group_m(int ntiles, int tiles_m, int BM, int BN) {
   return gm < 1 ? 1 : (gm > tiles_m ? tiles_m : gm);
 }
 
-// the configurations that have a persistent instantiation (the large-row tiles)
-constexpr bool persist_cfg(int cfg) { return cfg == 1 || cfg == 2 || cfg == CFG_BIG || cfg == CFG_XST; }
-
-template <typename T, typename TO, bool AK, bool BK_, int EPI>
-static const void* persist_kernel(int cfg) {
-  if constexpr (sizeof(T) == 2 && (EPI == GEMM_EPI_FWD || EPI == GEMM_EPI_MSE || EPI == GEMM_EPI_SCORE)) {
-    switch (cfg) {
-      case 1: return (const void*)mmad_gemm_kernel_p<T, TO, AK, BK_, 1, EPI>;
-      case 2: return (const void*)mmad_gemm_kernel_p<T, TO, AK, BK_, 2, EPI>;
-      case CFG_BIG: return (const void*)mmad_gemm_kernel_p<T, TO, AK, BK_, CFG_BIG, EPI>;
-      case CFG_XST:
-        if constexpr (xst_ok<T, EPI>()) return (const void*)mmad_gemm_kernel_p<T, TO, AK, BK_, CFG_XST, EPI>;
-        return nullptr;
-      default: return nullptr;
-    }
-  }
-  return nullptr;
-}
-
-namespace {
-std::mutex g_pcap_mu;
-std::map<long, int> g_pcap;   // (device, epi, cfg) -> resident blocks of the persistent kernel
-}  // namespace
-
-static int persist_capacity(const void* fn, int epi, int cfg) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  const long key = ((long)dev * 8 + epi) * 16 + cfg;
-  {
-    std::lock_guard<std::mutex> lk(g_pcap_mu);
-    auto it = g_pcap.find(key);
-    if (it != g_pcap.end()) return it->second;
-  }
-  int per_cu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, CFG_NT[cfg], 0) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    per_cu = 0;
-  }
-  const int cap = per_cu > 0 && cus > 0 ? (per_cu * cus) & ~7 : 0;   // a multiple of 8 (XCD labels)
-  std::lock_guard<std::mutex> lk(g_pcap_mu);
-  g_pcap[key] = cap;
-  return cap;
-}
-
-template <typename T, typename TO, bool AK, bool BK_, int EPI>
-static int launch_tiled(const T* A, int lda, const T* B, int ldb, int Mp, int Np, int K,
-                        const GemmEpi& ep_in, int cfg, hipStream_t s) {
-  // CFG 7 / 8 outside their epilogues (column partials, MSE, sigmoid / tanh):
-  // CFG 6, the same 256x256 tile
-  if (is_xst(cfg) && !xst_ok_rt(sizeof(T) == 2 ? MMAD_BF16 : MMAD_F32, EPI, ep_in)) cfg = xst_base(cfg);
-  const int BM = CFG_BM[cfg], BN = CFG_BN[cfg];
-  const int tiles_m = Mp / BM, tiles_n = Np / BN, ntiles = tiles_m * tiles_n;
-  GemmEpi ep = ep_in;
-  ep.tiles_n = tiles_n;
-  const int S = ep.splitk > 1 ? ep.splitk : 1;
-  ep.group_m = plan_group_m(ntiles, tiles_m, BM, BN);
-  // persistent grid: forward-type bf16 epilogues without a fused BN or a
-  // split, when the tiles exceed one resident round (knob 12: any nonzero
-  // value; with fewer tiles the ordinary grid is the same launch)
-  const int pk = mmad_persist_override();
-  if (pk != 0 && S == 1 && !ep.bn_sync && persist_cfg(cfg)) {
-    const void* pfn = persist_kernel<T, TO, AK, BK_, EPI>(cfg);
-    const int cap = pfn ? persist_capacity(pfn, EPI, cfg) : 0;
-    if (cap > 0 && ntiles > cap) {
-      ep.persist_tiles = ntiles;
-      dim3 pg(cap), pb(CFG_NT[cfg]);
-      auto args_go = [&](auto kern) {
-        if (ep.done_ev || ep.start_ev)
-          hipExtLaunchKernelGGL(kern, pg, pb, 0u, s, ep.start_ev, ep.done_ev, 0u, A, lda, B, ldb, K, ep);
-        else
-          kern<<<pg, pb, 0, s>>>(A, lda, B, ldb, K, ep);
-      };
-      if constexpr (sizeof(T) == 2 && (EPI == GEMM_EPI_FWD || EPI == GEMM_EPI_MSE || EPI == GEMM_EPI_SCORE)) {
-        switch (cfg) {
-          case 1: args_go(mmad_gemm_kernel_p<T, TO, AK, BK_, 1, EPI>); break;
-          case 2: args_go(mmad_gemm_kernel_p<T, TO, AK, BK_, 2, EPI>); break;
-          case CFG_XST:
-            if constexpr (xst_ok<T, EPI>()) {
-              args_go(mmad_gemm_kernel_p<T, TO, AK, BK_, CFG_XST, EPI>);
-              break;
-            }
-            [[fallthrough]];
-          default: args_go(mmad_gemm_kernel_p<T, TO, AK, BK_, CFG_BIG, EPI>); break;
-        }
-        MMAD_LAUNCH_CHECK();
-        return MMAD_OK;
-      }
-    }
-  }
-  if (cfg == CFG_B4) {
-    if constexpr (xst_ok<T, EPI>()) return mmad_gemm_b4_launch(EPI, A, lda, B, ldb, Mp, Np, K, ep, s);
-  }
-  dim3 grd(ntiles * S), blk(CFG_NT[cfg]);
-  const size_t dyn = 0;
-  // the caller's completion event rides on the launch itself (no marker packet)
-  auto go = [&](auto kern) {
-    if (ep.done_ev || ep.start_ev)
-      hipExtLaunchKernelGGL(kern, grd, blk, (std::uint32_t)dyn, s, ep.start_ev, ep.done_ev, 0u, A, lda, B, ldb,
-                            K, ep);
-    else
-      kern<<<grd, blk, dyn, s>>>(A, lda, B, ldb, K, ep);
-  };
-  switch (cfg) {
-    case 0: go(mmad_gemm_kernel<T, TO, AK, BK_, 0, EPI>); break;
-    case 1: go(mmad_gemm_kernel<T, TO, AK, BK_, 1, EPI>); break;
-    case 2: go(mmad_gemm_kernel<T, TO, AK, BK_, 2, EPI>); break;
-    case 3: go(mmad_gemm_kernel<T, TO, AK, BK_, 3, EPI>); break;
-    case 4: go(mmad_gemm_kernel<T, TO, AK, BK_, 4, EPI>); break;
-    case 5: go(mmad_gemm_kernel<T, TO, AK, BK_, 5, EPI>); break;
-    case CFG_XST1:
-      if constexpr (xst_ok<T, EPI>()) go(mmad_gemm_kernel<T, TO, AK, BK_, CFG_XST1, EPI>);
-      else go(mmad_gemm_kernel<T, TO, AK, BK_, 1, EPI>);
-      break;
-    default:
-      if constexpr (big_ok<T, EPI>()) {
-        if constexpr (xst_ok<T, EPI>()) {
-          if (cfg == CFG_XST) {
-            go(mmad_gemm_kernel<T, TO, AK, BK_, CFG_XST, EPI>);
-            break;
-          }
-        }
-        go(mmad_gemm_kernel<T, TO, AK, BK_, CFG_BIG, EPI>);
+// ---- the kernel table: (tile, persistent) -> instantiation, or null --------
+// Generated from TILES: tile C is instantiated for the (operand type,
+// epilogue) pairs its kind takes (big_ok / xst_ok), its persistent form for
+// the forward-type bf16 pairs (big_ok's) if the table gives it one.
+template <typename T, typename TO, bool AK, bool BK_, int EPI, int C = 0>
+static const void* kernel_of(int cfg, bool persistent) {
+  if constexpr (C < NCFG) {
+    if (cfg != C) return kernel_of<T, TO, AK, BK_, EPI, C + 1>(cfg, persistent);
+    constexpr Tile t = TILES[C];
+    if constexpr ((!t.big || big_ok<T, EPI>()) && (!t.xst || xst_ok<T, EPI>())) {
+      if (persistent) {
+        if constexpr (t.persist && big_ok<T, EPI>()) return (const void*)mmad_gemm_kernel_p<T, TO, AK, BK_, C, EPI>;
+      } else if constexpr (C == CFG_B4) {
+        return mmad_gemm_b4_kernel(EPI);   // compiled in the 4-wave translation unit
       } else {
-        mmad_set_error("gemm: tile configuration %d does not support this dtype / epilogue", cfg);
-        return MMAD_EUNSUPPORTED;
+        return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, C, EPI>;
       }
-      break;
-  }
-  MMAD_LAUNCH_CHECK();
-  return MMAD_OK;
-}
-
-// ---- co-residency of a whole grid (the fused-BN column barrier needs it) ----
-template <typename T, typename TO, bool AK, bool BK_, int EPI>
-static const void* kernel_ptr(int cfg) {
-  switch (cfg) {
-    case 0: return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, 0, EPI>;
-    case 1: return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, 1, EPI>;
-    case 2: return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, 2, EPI>;
-    case 3: return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, 3, EPI>;
-    case 4: return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, 4, EPI>;
-    case 5: return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, 5, EPI>;
-    case CFG_XST1:
-      if constexpr (xst_ok<T, EPI>()) return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, CFG_XST1, EPI>;
-      return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, 1, EPI>;
-    default:
-      if constexpr (xst_ok<T, EPI>())
-        if (cfg == CFG_XST) return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, CFG_XST, EPI>;
-      if constexpr (big_ok<T, EPI>()) return (const void*)mmad_gemm_kernel<T, TO, AK, BK_, CFG_BIG, EPI>;
-      return nullptr;
-  }
-}
-static const void* kernel_for(int dtype, int epi, int cfg) {
-  if (dtype == MMAD_BF16) {
-    if (epi == GEMM_EPI_FWD) return kernel_ptr<bf16, bf16, true, true, GEMM_EPI_FWD>(cfg);
-    if (epi == GEMM_EPI_BWD_DATA) return kernel_ptr<bf16, bf16, true, false, GEMM_EPI_BWD_DATA>(cfg);
-  } else {
-    if (epi == GEMM_EPI_FWD) return kernel_ptr<float, float, true, true, GEMM_EPI_FWD>(cfg);
-    if (epi == GEMM_EPI_BWD_DATA) return kernel_ptr<float, float, true, false, GEMM_EPI_BWD_DATA>(cfg);
+    }
   }
   return nullptr;
 }
+static const void* kernel_for(int dtype, int epi, int cfg, bool persistent) {
+#define MMAD_EPIS(T)                                                                              \
+  switch (epi) {                                                                                  \
+    case GEMM_EPI_FWD: return kernel_of<T, T, true, true, GEMM_EPI_FWD>(cfg, persistent);         \
+    case GEMM_EPI_MSE: return kernel_of<T, T, true, true, GEMM_EPI_MSE>(cfg, persistent);         \
+    case GEMM_EPI_SCORE: return kernel_of<T, T, true, true, GEMM_EPI_SCORE>(cfg, persistent);     \
+    case GEMM_EPI_BWD_DATA: return kernel_of<T, T, true, false, GEMM_EPI_BWD_DATA>(cfg, persistent); \
+    case GEMM_EPI_BWD_WEIGHT:                                                                     \
+      return kernel_of<T, float, false, false, GEMM_EPI_BWD_WEIGHT>(cfg, persistent);             \
+  }                                                                                               \
+  return nullptr
+  if (dtype == MMAD_BF16) { MMAD_EPIS(bf16); }
+  MMAD_EPIS(float);
+#undef MMAD_EPIS
+}
+
+// ---- the capacity cache: blocks of a kernel resident on a device at once ----
+// CUs x min(occupancy API, the LDS bound); 0 if unknown.  The persistent grid
+// is this rounded down to a multiple of 8 (XCD labels); a fused-BN grid must
+// not exceed it (its column barrier needs every block resident).
 namespace {
-std::mutex g_occ_mu;
-std::map<long, int> g_occ;   // (device, dtype, epi, cfg) -> resident grid capacity
+std::mutex g_cap_mu;
+std::map<std::pair<int, const void*>, int> g_cap;   // (device, kernel) -> resident blocks
 }  // namespace
 
-// blocks of (dtype, epi, cfg) that can be resident on the current device at
-// once: CUs x min(occupancy API, the LDS bound); 0 if unknown
-static int grid_capacity(int dtype, int epi, int cfg) {
+static int kernel_capacity(const void* fn, int threads) {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  const long key = (((long)dev * 4 + dtype) * 8 + epi) * 16 + cfg;
+  if (!fn || hipGetDevice(&dev) != hipSuccess) return 0;
+  const auto key = std::make_pair(dev, fn);
   {
-    std::lock_guard<std::mutex> lk(g_occ_mu);
-    auto it = g_occ.find(key);
-    if (it != g_occ.end()) return it->second;
+    std::lock_guard<std::mutex> lk(g_cap_mu);
+    auto it = g_cap.find(key);
+    if (it != g_cap.end()) return it->second;
   }
-  const void* fn = kernel_for(dtype, epi, cfg);
   int per_cu = 0, cus = 0;
-  if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, CFG_NT[cfg], 0) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     per_cu = 0;
-  }
   hipFuncAttributes fa{};
-  if (fn && hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.sharedSizeBytes > 0) {
+  if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.sharedSizeBytes > 0) {
     const int lds_bound = (int)(163840 / fa.sharedSizeBytes);
     per_cu = per_cu < lds_bound ? per_cu : lds_bound;
   }
   (void)hipGetLastError();
   const int cap = per_cu > 0 && cus > 0 ? per_cu * cus : 0;
-  std::lock_guard<std::mutex> lk(g_occ_mu);
-  g_occ[key] = cap;
+  std::lock_guard<std::mutex> lk(g_cap_mu);
+  g_cap[key] = cap;
   return cap;
 }
 
-static bool coresident(int dtype, int epi, int cfg, int Mp, int Np) {
-  return mmad_gemm_ntiles(cfg, Mp, Np) <= grid_capacity(dtype, epi, cfg);
+// the whole grid of an allowed `cfg` resident at once
+static bool coresident(int cfg, const GemmProblem& p) {
+  const int run = tile_runs(cfg, p);
+  return mmad_gemm_ntiles(run, p.Mp, p.Np) <=
+         kernel_capacity(kernel_for(p.dtype, p.epi, run, false), TILES[run].NT);
 }
 
 bool mmad_gemm_bn_fusable(int dtype, int epi, int Mp, int Np) {
-  if (epi != GEMM_EPI_FWD && epi != GEMM_EPI_BWD_DATA) return false;
   if (Mp % 128 || Np % 128 || Np / 64 > MMAD_BN_EXIT) return false;
+  const GemmProblem p{dtype, epi, Mp, Np, 1, true, false, MMAD_ACT_NONE};
   for (int c = 0; c < NCFG; ++c)
-    if (cfg_fits(c, Mp, Np, epi, dtype) && !is_big(c) && !is_xst(c) && coresident(dtype, epi, c, Mp, Np))
-      return true;
+    if (tile_allowed(c, p) && coresident(c, p)) return true;
   return false;
 }
 
-static int launch_cfg(int dtype, int epi, const void* A, int lda, const void* B, int ldb, int Mp,
-                      int Np, int K, const GemmEpi& ep, int cfg, hipStream_t s) {
-#define MMAD_LT(T, TO, AK, BK_, EPI)                                                      \
-  return launch_tiled<T, TO, AK, BK_, EPI>((const T*)A, lda, (const T*)B, ldb, Mp, Np, K, ep, cfg, s)
-#define MMAD_DISPATCH_T(T)                                                               \
-  switch (epi) {                                                                         \
-    case GEMM_EPI_FWD: MMAD_LT(T, T, true, true, GEMM_EPI_FWD);                          \
-    case GEMM_EPI_MSE: MMAD_LT(T, T, true, true, GEMM_EPI_MSE);                          \
-    case GEMM_EPI_SCORE: MMAD_LT(T, T, true, true, GEMM_EPI_SCORE);                      \
-    case GEMM_EPI_BWD_DATA: MMAD_LT(T, T, true, false, GEMM_EPI_BWD_DATA);               \
-    case GEMM_EPI_BWD_WEIGHT: MMAD_LT(T, float, false, false, GEMM_EPI_BWD_WEIGHT);      \
-    default: mmad_set_error("gemm: bad epilogue %d", epi); return MMAD_EINVAL;          \
+// launch the kernel of `cfg` (a tile_runs result) for `p`
+static int launch_tile(const GemmProblem& p, int cfg, const void* A, int lda, const void* B, int ldb, int K,
+                       const GemmEpi& ep_in, hipStream_t s) {
+  const Tile& t = TILES[cfg];
+  const int tiles_m = p.Mp / t.BM, tiles_n = p.Np / t.BN, ntiles = tiles_m * tiles_n;
+  GemmEpi ep = ep_in;
+  ep.tiles_n = tiles_n;
+  ep.group_m = plan_group_m(ntiles, tiles_m, t.BM, t.BN);
+  const void* fn = kernel_for(p.dtype, p.epi, cfg, false);
+  int grid = ntiles * p.splitk;
+  if (!fn) {
+    mmad_set_error("gemm: tile configuration %d does not support this dtype / epilogue", cfg);
+    return MMAD_EUNSUPPORTED;
   }
-  if (dtype == MMAD_BF16) {
-    MMAD_DISPATCH_T(bf16)
-  } else {
-    MMAD_DISPATCH_T(float)
+  // persistent grid: forward-type bf16 epilogues without a fused BN or a
+  // split, when the tiles exceed one resident round (knob 12: any nonzero
+  // value; with fewer tiles the ordinary grid is the same launch)
+  if (mmad_persist_override() != 0 && p.splitk == 1 && !p.fused_bn && t.persist) {
+    const void* pfn = kernel_for(p.dtype, p.epi, cfg, true);
+    const int cap = kernel_capacity(pfn, t.NT) & ~7;
+    if (cap > 0 && ntiles > cap) {
+      ep.persist_tiles = ntiles;
+      fn = pfn;
+      grid = cap;
+    }
   }
-#undef MMAD_LT
-#undef MMAD_DISPATCH_T
+  void* args[] = {&A, &lda, &B, &ldb, &K, &ep};
+  return mmad_gemm_launch(fn, dim3(grid), dim3(t.NT), s, ep.start_ev, ep.done_ev, args);
 }
 
 // ---- autotune: time every fitting tile config once per problem shape -------
@@ -2312,8 +2232,9 @@ std::mutex g_tune_mu;
 std::map<TuneKey, int> g_tune;
 }  // namespace
 
-static int tune_cfg(int dtype, int epi, const void* A, int lda, const void* B, int ldb, int Mp,
-                    int Np, int K, const GemmEpi& ep, hipStream_t s, int* out_cfg) {
+template <typename Pred>
+static int tune_cfg(const GemmProblem& p, Pred allowed, const void* A, int lda, const void* B, int ldb, int K,
+                    const GemmEpi& ep, hipStream_t s, int* out_cfg) {
   // the trial launches must be side-effect free beyond the outputs the real
   // launch rewrites: no fused Adam while timing
   GemmEpi et = ep;
@@ -2330,16 +2251,15 @@ static int tune_cfg(int dtype, int epi, const void* A, int lda, const void* B, i
   float best_ms = 1e30f;
   int rc = MMAD_OK;
   for (int c = 0; c < NCFG && rc == MMAD_OK; ++c) {
-    if (!cfg_fits(c, Mp, Np, epi, dtype)) continue;
-    if ((is_big(c) || is_xst(c)) && (ep.bn_sync || ep.splitk > 1)) continue;   // no fused BN / split
+    if (!allowed(c)) continue;
     if (c == CFG_B4) continue;   // the 4-wave tile: forced only (measured slower)
-    if (ep.bn_sync && !coresident(dtype, epi, c, Mp, Np)) continue;
-    rc = launch_cfg(dtype, epi, A, lda, B, ldb, Mp, Np, K, et, c, s);   // warm
+    const int run = tile_runs(c, p);
+    rc = launch_tile(p, run, A, lda, B, ldb, K, et, s);   // warm
     if (rc != MMAD_OK) break;
     float ms = 0.f;
     hipError_t e = hipEventRecord(e0, s);
     for (int r = 0; r < 3 && rc == MMAD_OK && e == hipSuccess; ++r)
-      rc = launch_cfg(dtype, epi, A, lda, B, ldb, Mp, Np, K, et, c, s);
+      rc = launch_tile(p, run, A, lda, B, ldb, K, et, s);
     if (rc != MMAD_OK) break;
     if (e == hipSuccess) e = hipEventRecord(e1, s);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
@@ -2355,7 +2275,7 @@ static int tune_cfg(int dtype, int epi, const void* A, int lda, const void* B, i
   (void)hipEventDestroy(e1);
   if (rc != MMAD_OK) return rc;
   if (best < 0) {
-    mmad_set_error("gemm autotune: no tile configuration fits (Mp=%d Np=%d epi=%d)", Mp, Np, epi);
+    mmad_set_error("gemm autotune: no tile configuration fits (Mp=%d Np=%d epi=%d)", p.Mp, p.Np, p.epi);
     return MMAD_EUNSUPPORTED;
   }
   *out_cfg = best;
@@ -2440,11 +2360,16 @@ int mmad_gemm_read_status(unsigned* ctl, hipStream_t s, const char* who) {
 }
 
 int mmad_gemm_plan(int Mp, int Np, int K, int epi, int dtype) {
-  const int env = mmad_tile_override();
-  if (env >= 0 && env < NCFG && cfg_fits(env, Mp, Np, epi, dtype)) return env;
-  std::lock_guard<std::mutex> lk(g_tune_mu);
-  auto it = g_tune.find(TuneKey{dtype, epi, Mp, Np, K, 0});
-  return it != g_tune.end() ? it->second : heuristic_cfg(Mp, Np, epi, dtype);
+  // the plain problem of the shape: no split, fused BN, partials or activation
+  const GemmProblem p{dtype, epi, Mp, Np, 1, false, false, MMAD_ACT_NONE};
+  auto allowed = [&](int c) { return tile_allowed(c, p); };
+  int cfg = mmad_tile_override();
+  if (!allowed(cfg)) {
+    std::lock_guard<std::mutex> lk(g_tune_mu);
+    auto it = g_tune.find(TuneKey{dtype, epi, Mp, Np, K, 0});
+    cfg = it != g_tune.end() ? it->second : heuristic_cfg(Mp, Np, allowed);
+  }
+  return cfg < 0 ? cfg : tile_runs(cfg, p);
 }
 
 int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B, int ldb, int Mp,
@@ -2460,6 +2385,7 @@ int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B
     return mmad_gemm_x3_dispatch(epi, A, lda, B, ldb, Mp, Np, K, ex, s);
   }
   MMAD_CHECK_ARG(dtype == MMAD_BF16 || dtype == MMAD_F32, "gemm: bad dtype %d", dtype);
+  MMAD_CHECK_ARG(epi >= GEMM_EPI_FWD && epi <= GEMM_EPI_SCORE, "gemm: bad epilogue %d", epi);
   GemmEpi ep = ep_in;
   ep.dbg = mmad_dbg_override();
   const bool bnf = ep.bn_sync != nullptr;
@@ -2469,11 +2395,8 @@ int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B
   // the fused BN barrier needs one block per output tile (no split) and the
   // whole grid resident
   ep.splitk = (ep.sk_slab && ep.sk_ctl && !bnf) ? mmad_gemm_splitk(Mp, Np, K, dtype, epi) : 1;
-  auto allowed = [&](int c) {
-    return c >= 0 && c < NCFG && cfg_fits(c, Mp, Np, epi, dtype) &&
-           ((!is_big(c) && !is_xst(c)) || ep.splitk <= 1) &&
-           (!bnf || (!is_big(c) && !is_xst(c) && coresident(dtype, epi, c, Mp, Np)));
-  };
+  const GemmProblem p{dtype, epi, Mp, Np, ep.splitk, bnf, ep.part || ep.bpart, ep.act};
+  auto allowed = [&](int c) { return tile_allowed(c, p) && (!bnf || coresident(c, p)); };
   const int env = mmad_tile_override();
   const int env_epi = ep.ad_p ? mmad_tile_adam_for(Mp, Np, K) : mmad_tile_epi_override(epi);
   int cfg;
@@ -2498,10 +2421,10 @@ int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
       (void)hipStreamIsCapturing(s, &cs);
       if (mmad_autotune_enabled() && cs == hipStreamCaptureStatusNone) {
-        int rc = tune_cfg(dtype, epi, A, lda, B, ldb, Mp, Np, K, ep, s, &cfg);
+        int rc = tune_cfg(p, allowed, A, lda, B, ldb, K, ep, s, &cfg);
         if (rc != MMAD_OK) return rc;
       } else {
-        cfg = heuristic_cfg(Mp, Np, epi, allowed);
+        cfg = heuristic_cfg(Mp, Np, allowed);
         if (cfg < 0) {
           mmad_set_error("gemm: no co-resident tile configuration for the fused BN epilogue "
                          "(Mp=%d Np=%d)", Mp, Np);
@@ -2512,7 +2435,8 @@ int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B
       g_tune[key] = cfg;
     }
   }
-  if (cfg_used) *cfg_used = cfg;
-  return launch_cfg(dtype, epi, A, lda, B, ldb, Mp, Np, K, ep, cfg, s);
+  const int run = tile_runs(cfg, p);
+  if (cfg_used) *cfg_used = run;
+  return launch_tile(p, run, A, lda, B, ldb, K, ep, s);
 }
 #endif  // MMAD_GEMM_B4_TU

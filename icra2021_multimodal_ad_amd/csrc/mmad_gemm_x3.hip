@@ -275,15 +275,8 @@ int mmad_gemm_x3_dispatch(int epi, const void* A, int lda, const void* B, int ld
   const int tiles_m = Mp / X_BM, tiles_n = Np / X_BN, ntiles = tiles_m * tiles_n;
   ep.tiles_n = tiles_n;
   ep.group_m = x_group_m(ntiles, tiles_m);
-  dim3 grd(ntiles), blk(X_NT);
-  auto go = [&](auto kern) {
-    if (ep.done_ev || ep.start_ev)
-      hipExtLaunchKernelGGL(kern, grd, blk, 0u, s, ep.start_ev, ep.done_ev, 0u, ar, ep);
-    else
-      kern<<<grd, blk, 0, s>>>(ar, ep);
-  };
-  if (epi == GEMM_EPI_FWD) go(mmad_gemm_x3_kernel<GEMM_EPI_FWD>);
-  else go(mmad_gemm_x3_kernel<GEMM_EPI_SCORE>);
-  MMAD_LAUNCH_CHECK();
-  return MMAD_OK;
+  const void* fn = epi == GEMM_EPI_FWD ? (const void*)mmad_gemm_x3_kernel<GEMM_EPI_FWD>
+                                       : (const void*)mmad_gemm_x3_kernel<GEMM_EPI_SCORE>;
+  void* args[] = {&ar, &ep};
+  return mmad_gemm_launch(fn, dim3(ntiles), dim3(X_NT), s, ep.start_ev, ep.done_ev, args);
 }

@@ -131,6 +131,22 @@ int mmad_tune_get(int knob, int* value);
  * output, K deep) with epilogue `epi` (0 fwd, 1 MSE, 2 bwd-data, 3 dW,
  * 4 score) under the current knobs: 1, 2, 4, 8 or 16 (query only). */
 int mmad_gemm_splitk_for(int Mp, int Np, int K, int dtype, int epi);
+/* The GEMM tile whose kernel runs when tile `forced_cfg` (0-9) is forced
+ * through knob 0 for a padded Mp x Np problem of `dtype` (MMAD_F32 /
+ * MMAD_BF16) and epilogue `epi` (as above) with split factor `splitk`
+ * (1 = none), a fused train-mode BN or not, column partials (BN statistics /
+ * folded-BN bias partials) present or not, and activation `act`: forced_cfg
+ * itself, or the row-quad tile of the same shape a register-direct tile
+ * (7, 8 -> 6; 9 -> 1) runs as with partials or a non-piecewise-linear
+ * activation; -1 when that tile may not be chosen for the problem (the
+ * dispatcher then takes the tuned one).  A pure function of its arguments: it
+ * reads no knob and touches no device (query only).
+ *
+ * The knob table and these two queries describe the dispatcher of this build;
+ * they are not covered by MMAD_ABI_VERSION (a knob or a tile may be added or
+ * retired without bumping it). */
+int mmad_gemm_tile_for(int forced_cfg, int dtype, int epi, int Mp, int Np, int splitk, int fused_bn,
+                       int has_partials, int act);
 
 /* ------------------------------------------------------------------------
  * Layer operators

@@ -239,8 +239,15 @@ def test_persistent_grid_bit_identical(kind):
         call("mmad_fc_fwd_mse", BF16, M, N, K, Mp, Np, Kp, ptr(x), ptr(w), ptr(b), ptr(tgt), N, 2.0,
              ptr(y), ptr(part), s)
         return y, part
+    # the tile that runs is the forced one -- but tile 7 (register-direct) runs
+    # as tile 6 with BN-statistic partials, and the MSE epilogue does not take
+    # it at all (the tuned tile runs)
+    epi, parts, act = {"fwd": (0, 1, 1), "fwdns": (0, 0, 1), "score": (4, 0, 1), "mse": (1, 1, 0)}[kind]
+    split = lib.mmad_gemm_splitk_for(Mp, Np, Kp, BF16, epi)
     try:
         for tile in (1, 2, 6, 7):
+            want = tile if tile != 7 else {"fwd": 6, "fwdns": 7, "score": 7, "mse": -1}[kind]
+            assert lib.mmad_gemm_tile_for(tile, BF16, epi, Mp, Np, split, 0, parts, act) == want, (kind, tile)
             lib.mmad_tune_set(0, tile)
             lib.mmad_tune_set(12, 0)
             a = run()
@@ -306,9 +313,20 @@ def test_register_direct_tile_bit_identical(case, N):
              ptr(sh), ptr(y), ptr(ref), ptr(rows),
              ptr(diff) if case == "score_ref_diff" else None, N, s)
         return y, rows, diff
+    # the tile that runs: the forced one; its row-quad twin in the two
+    # *_fallback cases; the tuned one (-1) where a 256-column tile does not
+    # divide 1664 columns
+    epi, parts, act = {"fwd_leaky_bn": (0, 0, 1), "fwd_relu": (0, 0, 2), "fwd_none": (0, 0, 0),
+                       "score_ref_diff": (4, 0, 1), "score_nodiff": (4, 0, 1), "nap_colw": (4, 0, 0),
+                       "fwd_stats_fallback": (0, 1, 1), "fwd_sigmoid_fallback": (0, 0, 3)}[case]
+    split = lib.mmad_gemm_splitk_for(Mp, Np, Kp, BF16, epi)
     outs = {}
     try:
         for tile in (6, 7, 8, 1, 2, 9):
+            want = {7: 6, 8: 6, 9: 1}.get(tile, tile) if case.endswith("_fallback") else tile
+            if Np % 256 and tile in (2, 6, 7, 8):
+                want = -1
+            assert lib.mmad_gemm_tile_for(tile, BF16, epi, Mp, Np, split, 0, parts, act) == want, (case, tile)
             lib.mmad_tune_set(0, tile)
             outs[tile] = run()
         torch.cuda.synchronize()
@@ -318,6 +336,61 @@ def test_register_direct_tile_bit_identical(case, N):
     for tile in (7, 8, 1, 2, 9):
         for a, b2 in zip(outs[6], outs[tile]):
             assert torch.equal(a, b2), (case, tile)
+
+
+@pytest.mark.parametrize("events", [False, True])
+def test_tile8_smallest_problem_bit_identical(events):
+    """Tile 8's kernels live in a translation unit of their own and are
+    launched by address through the one launch path.  Its smallest problem
+    (bf16, 256 x 256 output, K = 128: one tile, one pair of K stages) must
+    equal tile 6 bit for bit -- on a plain stream through mmad_fc_fwd, and
+    with start / stop events riding on the launch, which from Python is
+    reachable through the executor's kernel-attached probe (kind 2) on the
+    eval forward of a 128 -> 256 layer at 256 rows."""
+    import ctypes
+    lib = _native.load()
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cuda").manual_seed(21)
+    M, N, K = 256, 256, 128
+    for tile, act in ((6, 1), (8, 1), (8, 0)):
+        assert lib.mmad_gemm_tile_for(tile, BF16, 0, M, N, lib.mmad_gemm_splitk_for(M, N, K, BF16, 0),
+                                      0, 0, act) == tile
+    outs = {}
+    if not events:
+        x = torch.randn(M, K, device=dev, generator=g).bfloat16()
+        w = (torch.randn(N, K, device=dev, generator=g) * 0.05).bfloat16()
+        b = torch.randn(N, device=dev, generator=g) * 0.1
+        try:
+            for tile in (6, 8):
+                lib.mmad_tune_set(0, tile)
+                y = torch.zeros(M, N, device=dev, dtype=torch.bfloat16)
+                call("mmad_fc_fwd", BF16, M, N, K, M, N, K, ptr(x), ptr(w), ptr(b), 1, 0.2, None, None,
+                     ptr(y), None, stream_ptr())
+                outs[tile] = y
+            torch.cuda.synchronize()
+        finally:
+            lib.mmad_tune_set(0, -1)
+    else:
+        from icra2021_multimodal_ad_amd.engine import NativeAE
+        nat = NativeAE([K, N, 128], [128, K], dtype="bf16", device=dev)   # layer 0: 128 -> 256, BN, LeakyReLU
+        nat.params.copy_(torch.randn(nat.n_params, device=dev, generator=g) * 0.05)
+        nat.sync_shadow(force=True)
+        x = torch.randn(M, K, device=dev, generator=g)
+        buf = (ctypes.c_float * 1)()
+        try:
+            for tile in (6, 8):
+                lib.mmad_tune_set(0, tile)
+                if tile == 8:
+                    assert lib.mmad_ae_probe(nat._h, 2, 0, 1) == 0
+                outs[tile] = nat.forward(x)[0]
+            torch.cuda.synchronize()
+            assert lib.mmad_ae_probe_read(nat._h, buf, 1) == 1      # the launch completed both events
+            assert lib.mmad_ae_probe_layers(nat._h) == 1 and buf[0] > 0.0
+        finally:
+            lib.mmad_tune_set(0, -1)
+            lib.mmad_ae_probe(nat._h, 1, -1, 0)
+    assert float(outs[6].float().abs().sum()) > 0
+    assert torch.equal(outs[6], outs[8])
 
 
 @pytest.mark.parametrize("blocks", [256, 512])

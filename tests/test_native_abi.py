@@ -58,6 +58,8 @@ def test_abi_constants_and_errors(lib):
     assert rc == -1
     assert b"multiples of 128" in lib.mmad_last_error_string()
     assert lib.mmad_tune_set(99, 0) == -1
+    # the dispatcher queries are pure host functions (tests/test_gemm_tiles.py)
+    assert lib.mmad_gemm_tile_for(7, 1, 0, 256, 256, 1, 0, 1, 0) == 6
 
 
 def test_tune_table_names_and_defaults(lib):
