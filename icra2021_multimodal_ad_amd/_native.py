@@ -85,6 +85,10 @@ SIGNATURES = {
     "mmad_ae_forward": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _I64, _P]),
     "mmad_ae_score": (_I, [_P, _P, _I, _I, _P, _P, _P, _I64, _P]),
     "mmad_ae_score_stream": (_I, [_P, _P, _I, _I64, _I, _P, _I64, _P, _I64, _I, _P]),
+    "mmad_ae_set_nap": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "mmad_ae_score_nap": (_I, [_P, _P, _I, _I, _P, _P, _P, _I64, _P]),
+    "mmad_ae_score_nap_stream": (_I, [_P, _P, _I, _I64, _I, _P, _I64, _P, _P, _I64, _I, _P]),
+    "mmad_ae_nap_operand": (_I, [_P, _I, ctypes.POINTER(_I64)]),
     "mmad_ae_status": (_I, [_P, _P, _I64, _P]),
     "mmad_ae_probe": (_I, [_P, _I, _I, _I]),
     "mmad_ae_probe_read": (_I, [_P, ctypes.POINTER(_F), _I]),

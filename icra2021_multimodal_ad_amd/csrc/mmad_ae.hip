@@ -67,6 +67,17 @@ struct mmad_ae {
   // written since the last split; the scoring entry points re-split first
   void* planes = nullptr;
   bool planes_stale = true;
+  // streamed NAP (mmad_ae_set_nap): the fit of the concatenated diffs of the
+  // diff layers [start, end) (0 = x_hat - x, 1 + e = encoder layer e), all
+  // caller-owned.  dtype: the NAP GEMM's (MMAD_F32: fp32 operand written
+  // through the score GEMMs' diff output; MMAD_BF16X3: plane operand written
+  // through their diff-plane output, vt split into vt_planes at attach)
+  struct NapFit {
+    bool on = false;
+    int start = 0, end = 0, K = 0, Kp = 0, R = 0, Rp = 0, dtype = MMAD_F32;
+    const float *vt = nullptr, *bias = nullptr, *w = nullptr;
+    void* vt_planes = nullptr;
+  } nap;
   // side stream + events for the dW / Adam overlap (created at bind time)
   hipStream_t side = nullptr;
   std::vector<hipEvent_t> ev_fork, ev_data;
@@ -181,6 +192,8 @@ struct mmad_ae {
   struct ScoreGraph {
     const float* x; int64_t ld_x, N; int batch; float* sq; int64_t ld_sq; void* ws;
     const void* wts;   // weight operand base (the bf16 shadow may be re-pointed)
+    float* nap;        // NAP output (null: a pass without it) and the fit it was captured with
+    const void* nap_vt;
     hipGraphExec_t exec;
   };
   std::vector<ScoreGraph> graphs;
@@ -281,6 +294,11 @@ struct AeWS {
   bool ping = false;
   int dw_main = 2;
   std::vector<LayerWS> l;
+  // streamed NAP (a fit attached, else null): the packed operand [Mpe][nap.Kp]
+  // (fp32, or bf16 planes [2][Mpe][nap.Kp]) and the NAP GEMM's row partials
+  void* nap_x = nullptr;
+  float* nap_rowsq = nullptr;
+  int64_t nap_x_off = -1;   // byte offset of nap_x in the workspace
   int64_t bytes;
 };
 
@@ -389,6 +407,16 @@ static void carve(const mmad_ae* h, int B, int k, char* base, AeWS& w) {
   for (int i = 0; i < nL; ++i) {
     const AeLayer& a = h->L[i];
     w.l[i].ref32 = (h->planes && a.enc) ? (float*)take((int64_t)w.Mpe * a.Np * 4) : nullptr;
+  }
+  // streamed NAP: after those, so neither attachment moves the other's offsets
+  // (both element types fill the same bytes: 4 per operand element)
+  w.nap_x = nullptr;
+  w.nap_rowsq = nullptr;
+  w.nap_x_off = -1;
+  if (h->nap.on) {
+    w.nap_x = take((int64_t)w.Mpe * h->nap.Kp * 4);
+    w.nap_x_off = off - (int64_t)w.Mpe * h->nap.Kp * 4;
+    w.nap_rowsq = (float*)take((int64_t)(h->nap.Rp / 128) * w.Mpe * 4);
   }
   w.bytes = (off + 255) / 256 * 256;
 }
@@ -590,6 +618,66 @@ int mmad_ae_set_score_planes(mmad_ae* h, void* planes) {
 }
 
 int mmad_ae_score_dtype(const mmad_ae* h) { return h ? score_dt(h) : -1; }
+
+// first column of diff layer j in the concatenated diffs (j = n_enc + 1: their width)
+static int diff_col(const mmad_ae* h, int j) {
+  int c = 0;
+  for (int i = 0; i < j; ++i) c += i == 0 ? h->L[0].K : h->L[i - 1].N;
+  return c;
+}
+
+int mmad_ae_set_nap(mmad_ae* h, int start, int end, int R, const float* vt, const float* bias,
+                    const float* w, int dtype, void* vt_planes, void* stream) {
+  MMAD_CHECK_ARG(h, "ae_set_nap: null handle");
+  if (!vt) {   // detach
+    if (h->nap.on) {
+      h->nap = mmad_ae::NapFit{};
+      return mmad_ae_clear_graphs(h);
+    }
+    return MMAD_OK;
+  }
+  MMAD_CHECK_ARG(start >= 0 && end > start && end <= h->n_enc + 1,
+                 "ae_set_nap: bad layer range [%d, %d) of %d diff layers", start, end, h->n_enc + 1);
+  MMAD_CHECK_ARG(R >= 1 && bias && w, "ae_set_nap: bad fit (R=%d, null bias / w)", R);
+  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16X3,
+                 "ae_set_nap: the NAP GEMM runs as MMAD_F32 or MMAD_BF16X3 (dtype %d)", dtype);
+  mmad_ae::NapFit f;
+  f.on = true;
+  f.start = start;
+  f.end = end;
+  f.K = diff_col(h, end) - diff_col(h, start);
+  f.Kp = mmad_roundup(f.K, MMAD_PAD);
+  f.R = R;
+  f.Rp = mmad_roundup(R, MMAD_PAD);
+  f.dtype = dtype;
+  f.vt = vt;
+  f.bias = bias;
+  f.w = w;
+  if (dtype == MMAD_BF16X3) {
+    MMAD_CHECK_ARG(score_dt(h) == MMAD_BF16X3, "ae_set_nap: an MMAD_BF16X3 NAP GEMM needs score planes "
+                   "attached (mmad_ae_set_score_planes): its operand is written by the x3 score GEMMs");
+    MMAD_CHECK_ARG(vt_planes && ((uintptr_t)vt_planes) % 16 == 0 && ((uintptr_t)vt) % 16 == 0,
+                   "ae_set_nap: MMAD_BF16X3 needs 16-byte aligned vt and vt_planes");
+    f.vt_planes = vt_planes;
+    const int64_t n = (int64_t)f.Rp * f.Kp;
+    RET_IF(mmad_split_planes(n, vt, vt_planes, (char*)vt_planes + n * 2, stream));
+  }
+  h->nap = f;
+  return mmad_ae_clear_graphs(h);   // captured passes bake the operand layout and the fit's addresses in
+}
+
+int mmad_ae_nap_operand(const mmad_ae* h, int B, int64_t* info) {
+  MMAD_CHECK_ARG(h && info && B >= 1, "ae_nap_operand: bad arguments");
+  MMAD_CHECK_ARG(h->nap.on, "ae_nap_operand: no NAP fit attached");
+  AeWS w;
+  carve(h, B, 1, nullptr, w);
+  info[0] = w.nap_x_off;
+  info[1] = w.Mpe;
+  info[2] = h->nap.Kp;
+  info[3] = h->nap.K;
+  info[4] = h->nap.dtype;
+  return MMAD_OK;
+}
 
 int mmad_ae_sync_shadow(mmad_ae* h, void* stream) {
   MMAD_CHECK_ARG(h && h->params, "ae_sync_shadow: unbound");
@@ -1578,8 +1666,11 @@ int mmad_ae_forward(mmad_ae* h, const float* x, int ld_x, int B, int train_bn, f
 
 // one batch of the scoring pass on a prepared workspace; layer_sq row l at
 // layer_sq + l*ld_sq
+// nap (nullable; needs a fit and no caller diffs): the in-range score GEMMs
+// write their diffs straight into the packed NAP operand, then the NAP GEMM
+// and its column sum write nap[0..B)
 static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq,
-                       int64_t ld_sq, float* diffs, AeWS& w, hipStream_t st) {
+                       int64_t ld_sq, float* diffs, AeWS& w, hipStream_t st, float* nap = nullptr) {
   // x3 (score planes attached): activations travel as bf16 planes, every
   // reference of a diff stays fp32 -- pass 1 leaves an fp32 copy of each
   // encoder output (ref32), the decoder's last layer scores against the
@@ -1590,6 +1681,26 @@ static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer
   RET_IF(mmad_pack_input(dt, B, h->L[0].K, w.Mpe, h->L[0].Kp, x, ld_x, w.xin, st));
   int ld_diff = h->L[0].K;
   for (int e = 0; e < h->n_enc; ++e) ld_diff += h->L[e].N;
+  const mmad_ae::NapFit& nf = h->nap;
+  const bool nap_x3 = nap && nf.dtype == MMAD_BF16X3;
+  // route diff layer j's diffs into the operand (columns relative to the range's first)
+  auto nap_route = [&](GemmEpi& ep, int j) {
+    if (!nap || j < nf.start || j >= nf.end) return;
+    const int col = diff_col(h, j) - diff_col(h, nf.start);
+    if (nap_x3) {
+      ep.dp_hi = w.nap_x;
+      ep.dp_lo = (char*)w.nap_x + (size_t)w.Mpe * nf.Kp * 2;
+      ep.lddp = nf.Kp;
+      ep.dp_col = col;
+    } else {
+      ep.diff = (float*)w.nap_x + col;
+      ep.lddiff = nf.Kp;
+    }
+  };
+  // the operand's padding, every batch: a ragged batch's workspace is carved
+  // at other offsets than the full batches', so nothing survives from them
+  if (nap)
+    RET_IF(mmad_zero_pad(nap_x3 ? 2 : 4, nap_x3 ? 2 : 1, B, nf.K, w.Mpe, nf.Kp, w.nap_x, st));
   // pass 1: eval forward; the decoder's last layer scores d0 = x_hat - x
   for (int l = 0; l < nL; ++l) {
     const AeLayer& a = h->L[l];
@@ -1613,6 +1724,7 @@ static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer
       ep.ldrow = Mp;
       ep.diff = diffs;
       ep.lddiff = ld_diff;
+      nap_route(ep, 0);
       RET_IF(ae_gemm(h, w, dt, GEMM_EPI_SCORE, in, a.Kp, wt, a.Kp, Mp, a.Np, a.Kp, ep, st));
     } else {
       if (x3 && a.enc) {
@@ -1643,6 +1755,7 @@ static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer
     ep.ldrow = w.Mpe;
     ep.diff = diffs ? diffs + coff : nullptr;
     ep.lddiff = ld_diff;
+    nap_route(ep, e + 1);
     const void* wt = weights_dt(h, a, dt, ep);
     RET_IF(ae_gemm(h, w, dt, GEMM_EPI_SCORE, cur, a.Kp, wt, a.Kp, w.Mpe, a.Np, a.Kp, ep, st));
     coff += a.N;
@@ -1657,7 +1770,39 @@ static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer
     jobs.j[e + 1] = MmadReduceJob{w.l[e].rowsq, layer_sq + (size_t)(e + 1) * ld_sq,
                                   h->L[e].Np / 128, w.Mpe, B, B, 1.f, 0, nullptr, 0, 0.f};
   MMAD_CHECK_ARG(h->n_enc + 1 <= MMAD_MAX_REDUCE_JOBS, "too many encoder layers");
-  return mmad_reduce_jobs(jobs, h->n_enc + 1, B, st);
+  RET_IF(mmad_reduce_jobs(jobs, h->n_enc + 1, B, st));
+  if (!nap) return MMAD_OK;
+  // the NAP run as mmad_nap_score forms it: one SCORE GEMM (no reference, bias
+  // after the product, colw = w) and the column sum of its row partials
+  GemmEpi ep{};
+  ep.M = B; ep.N = nf.R; ep.out = nullptr; ep.ldo = nf.Rp; ep.bias = nf.bias; ep.act = MMAD_ACT_NONE;
+  ep.ref = nullptr; ep.ldref = nf.Rp; ep.rowsq = w.nap_rowsq; ep.ldrow = w.Mpe; ep.colw = nf.w;
+  const void* vt = nap_x3 ? (const void*)nf.vt_planes : (const void*)nf.vt;
+  RET_IF(ae_gemm(h, w, nf.dtype, GEMM_EPI_SCORE, w.nap_x, nf.Kp, vt, nf.Kp, w.Mpe, nf.Rp, nf.Kp, ep, st));
+  // (N = Np = B: nothing past nap[B) is written -- the next batch's scores, or the caller's memory)
+  return mmad_colsum(nf.Rp / 128, B, B, w.nap_rowsq, w.Mpe, 1.f / (float)nf.R, nap, st);
+}
+
+// a NAP-writing entry point's preconditions (nothing is launched on failure)
+static int check_nap(const mmad_ae* h, const float* nap, const char* who) {
+  MMAD_CHECK_ARG(nap, "%s: null nap output", who);
+  MMAD_CHECK_ARG(h->nap.on, "%s: no NAP fit attached (mmad_ae_set_nap)", who);
+  MMAD_CHECK_ARG(h->nap.dtype != MMAD_BF16X3 || score_dt(h) == MMAD_BF16X3,
+                 "%s: the attached fit's MMAD_BF16X3 NAP GEMM needs the score planes it was attached with", who);
+  return MMAD_OK;
+}
+
+int mmad_ae_score_nap(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq, float* nap,
+                      void* ws, int64_t ws_bytes, void* stream) {
+  MMAD_CHECK_ARG(h && h->params && h->running, "ae_score_nap: unbound handle");
+  MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && layer_sq, "ae_score_nap: bad args");
+  RET_IF(check_nap(h, nap, "ae_score_nap"));
+  AeWS w;
+  carve(h, B >= 1 ? B : 1, 1, nullptr, w);
+  MMAD_CHECK_ARG(B >= 1 && ws && ws_bytes >= w.bytes, "ae_score_nap: bad batch or workspace too small");
+  RET_IF(refresh_planes(h, (hipStream_t)stream));
+  RET_IF(prepare_ws(h, B, 1, ws, ws_bytes, w, (hipStream_t)stream));
+  return score_batch(h, x, ld_x, B, layer_sq, B, nullptr, w, (hipStream_t)stream, nap);
 }
 
 int mmad_ae_score(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq, float* diffs,
@@ -1677,19 +1822,21 @@ static const void* score_weights(const mmad_ae* h) {
 
 // the whole N-window pass, batch by batch, on stream st
 static int score_pass(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch, float* layer_sq,
-                      int64_t ld_sq, void* ws, int64_t ws_bytes, hipStream_t st) {
+                      int64_t ld_sq, float* nap, void* ws, int64_t ws_bytes, hipStream_t st) {
   for (int64_t s0 = 0; s0 < N; s0 += batch) {
     const int B = (int)std::min<int64_t>(batch, N - s0);
     AeWS w;
     RET_IF(prepare_ws(h, B, 1, ws, ws_bytes, w, st));
-    RET_IF(score_batch(h, x + s0 * ld_x, ld_x, B, layer_sq + s0, ld_sq, nullptr, w, st));
+    RET_IF(score_batch(h, x + s0 * ld_x, ld_x, B, layer_sq + s0, ld_sq, nullptr, w, st,
+                       nap ? nap + s0 : nullptr));
   }
   return MMAD_OK;
 }
 
-int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch,
-                         float* layer_sq, int64_t ld_sq, void* ws, int64_t ws_bytes, int use_graph,
-                         void* stream) {
+// the streaming pass, with the NAP output (nullable: the pass without NAP)
+static int score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch, float* layer_sq,
+                        int64_t ld_sq, float* nap, void* ws, int64_t ws_bytes, int use_graph,
+                        void* stream) {
   MMAD_CHECK_ARG(h && h->params && h->running, "ae_score_stream: unbound handle");
   MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && layer_sq && N >= 1 && batch >= 1 && ld_sq >= N,
                  "ae_score_stream: bad args (N=%lld batch=%d ld_sq=%lld)", (long long)N, batch,
@@ -1698,10 +1845,12 @@ int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int ba
   // stale score planes are re-split here, on the caller's stream and outside
   // the captured pass: a replay reads whatever the planes hold when it runs
   RET_IF(refresh_planes(h, st));
-  if (!use_graph) return score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, ws, ws_bytes, st);
+  const void* nap_vt = nap ? (const void*)h->nap.vt : nullptr;
+  if (!use_graph) return score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, st);
   for (auto& g : h->graphs) {
     if (g.x == x && g.ld_x == ld_x && g.N == N && g.batch == batch && g.sq == layer_sq &&
-        g.ld_sq == ld_sq && g.ws == ws && g.wts == score_weights(h)) {
+        g.ld_sq == ld_sq && g.ws == ws && g.wts == score_weights(h) && g.nap == nap &&
+        g.nap_vt == nap_vt) {
       MMAD_HIP_CHECK(hipGraphLaunch(g.exec, st));
       return MMAD_OK;
     }
@@ -1709,11 +1858,11 @@ int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int ba
   // first pass of this shape: run it eagerly (that also settles every GEMM
   // tile choice, which cannot be timed under capture), then capture the same
   // launches on the handle's capture stream for the next calls
-  RET_IF(score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, ws, ws_bytes, st));
+  RET_IF(score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, st));
   if (!h->gstream) MMAD_HIP_CHECK(hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking));
   hipGraph_t graph = nullptr;
   MMAD_HIP_CHECK(hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal));
-  const int rc = score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, ws, ws_bytes, h->gstream);
+  const int rc = score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, h->gstream);
   const hipError_t ec = hipStreamEndCapture(h->gstream, &graph);
   if (rc != MMAD_OK) {
     if (graph) (void)hipGraphDestroy(graph);
@@ -1728,8 +1877,24 @@ int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int ba
     (void)hipGraphExecDestroy(h->graphs.front().exec);
     h->graphs.erase(h->graphs.begin());
   }
-  h->graphs.push_back({x, ld_x, N, batch, layer_sq, ld_sq, ws, score_weights(h), exec});
+  h->graphs.push_back({x, ld_x, N, batch, layer_sq, ld_sq, ws, score_weights(h), nap, nap_vt, exec});
   return MMAD_OK;
+}
+
+int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch,
+                         float* layer_sq, int64_t ld_sq, void* ws, int64_t ws_bytes, int use_graph,
+                         void* stream) {
+  return score_stream(h, x, ld_x, N, batch, layer_sq, ld_sq, nullptr, ws, ws_bytes, use_graph, stream);
+}
+
+int mmad_ae_score_nap_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch,
+                             float* layer_sq, int64_t ld_sq, float* nap, void* ws, int64_t ws_bytes,
+                             int use_graph, void* stream) {
+  MMAD_CHECK_ARG(h, "ae_score_nap_stream: null handle");
+  RET_IF(check_nap(h, nap, "ae_score_nap_stream"));
+  MMAD_CHECK_ARG(batch >= 1 && ws && ws_bytes >= mmad_ae_workspace_bytes(h, batch, 1),
+                 "ae_score_nap_stream: bad batch or workspace too small");
+  return score_stream(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, use_graph, stream);
 }
 
 int mmad_ae_status(mmad_ae* h, void* ws, int64_t ws_bytes, void* stream) {

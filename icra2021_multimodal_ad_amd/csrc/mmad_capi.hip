@@ -172,7 +172,7 @@ static int check_dims(const char* who, int M, int N, int K, int Mp, int Np, int 
 static int check_dtype(int dtype, const char* who = "operator", bool x3_ok = false) {
   if (dtype == MMAD_BF16X3 && !x3_ok) {
     mmad_set_error("%s: MMAD_BF16X3 covers the eval / score path only (pack, unpack, fc_fwd "
-                   "without stats, fc_fwd_score, deterministic vib_reparam_fwd)", who);
+                   "without stats, fc_fwd_score, nap_score, deterministic vib_reparam_fwd)", who);
     return MMAD_EUNSUPPORTED;
   }
   MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16 || dtype == MMAD_BF16X3, "bad dtype %d",
@@ -271,14 +271,17 @@ int mmad_fc_fwd_score(int dtype, int M, int N, int K, int Mp, int Np, int Kp, co
 int mmad_nap_score(int dtype, int M, int K, int R, int Mp, int Kp, int Rp, const void* x,
                    const void* vt, const float* bias, const float* w, float* rowsq, float* score,
                    void* stream) {
-  RET_IF(check_dtype(dtype, "nap_score"));
+  // MMAD_BF16X3: x and vt are plane pairs ([2][Mp][Kp], [2][Rp][Kp]); the same
+  // SCORE epilogue (bias after the product, no reference, colw = w)
+  RET_IF(check_dtype(dtype, "nap_score", true));
   RET_IF(check_dims("nap_score", M, R, K, Mp, Rp, Kp));
   MMAD_CHECK_ARG(x && vt && bias && w && rowsq && score, "nap_score: null operand");
   GemmEpi ep{};
   ep.M = M; ep.N = R; ep.out = nullptr; ep.ldo = Rp; ep.bias = bias; ep.act = MMAD_ACT_NONE;
   ep.ref = nullptr; ep.ldref = Rp; ep.rowsq = rowsq; ep.ldrow = Mp; ep.colw = w;
   RET_IF(layer_gemm(dtype, GEMM_EPI_SCORE, x, Kp, vt, Kp, Mp, Rp, Kp, ep, stream));
-  return mmad_colsum(Rp / 128, M, Mp, rowsq, Mp, 1.f / (float)R, score, stream);
+  // score is [M]: no zero fill up to Mp (it ran past the caller's buffer)
+  return mmad_colsum(Rp / 128, M, M, rowsq, Mp, 1.f / (float)R, score, stream);
 }
 
 int mmad_fc_bwd_data(int dtype, int M, int N, int K, int Mp, int Np, int Kp, const void* dz,

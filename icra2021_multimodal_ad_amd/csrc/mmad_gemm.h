@@ -134,6 +134,15 @@ struct GemmEpi {
   // host only (nullable): an event that takes the launch's start time
   // (hipExtLaunchKernel's start event; the executor's in-step kernel probe)
   hipEvent_t start_ev;
+  // MMAD_BF16X3 SCORE only (nullable pair; last, so no other field moves): the
+  // fp32 diff d = y - ref written as split planes, hi = bf16(d), lo =
+  // bf16(d - hi), element (row, col) at dp_hi / dp_lo + row * lddp + dp_col +
+  // col.  Valid rows / columns only; lddp and dp_col are arbitrary (a layer's
+  // slot inside a concatenated operand may start at an odd column), so the
+  // stores are scalar, as the fp32 diff's are.
+  void* dp_hi;
+  void* dp_lo;
+  int lddp, dp_col;
 };
 
 int mmad_knob(int k);          // the tune table (mmad_tune_set)

@@ -21,6 +21,8 @@
 // ds_read_b128 per fragment).  The MFMA operands are swapped (B first), so a
 // lane's accumulator quad is 4 consecutive columns of one output row and the
 // epilogue stores straight from registers: 8 B per plane, 16 B of fp32.
+// The SCORE epilogue can also leave the fp32 diff as a plane pair inside a
+// caller's packed x3 operand (GemmEpi::dp_hi: the streamed NAP operand).
 // No split-K, no fused BN, no persistent grid; the K order is fixed, so the
 // result bits do not depend on the grid order.
 #include "mmad_common.h"
@@ -201,6 +203,11 @@ __global__ __launch_bounds__(X_NT, 1) void mmad_gemm_x3_kernel(X3Args ar, GemmEp
         // diff against the fp32 reference before anything is rounded to planes
         const float* rp = (const float*)ep.ref;
         float* dp = ep.diff ? ep.diff + (size_t)row * ep.lddiff + col0 : nullptr;
+        // ... and as split planes (a packed x3 operand's slot: scalar stores,
+        // any lddp / dp_col; rows >= M and columns >= N are not written)
+        const size_t po = (size_t)row * ep.lddp + ep.dp_col + col0;
+        bf16* ph = ep.dp_hi ? (bf16*)ep.dp_hi + po : nullptr;
+        bf16* pl = ep.dp_hi ? (bf16*)ep.dp_lo + po : nullptr;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const bool ok = rok && col0 + e < ep.N;
@@ -208,6 +215,11 @@ __global__ __launch_bounds__(X_NT, 1) void mmad_gemm_x3_kernel(X3Args ar, GemmEp
           const float d = y[e] - rv;
           rsum[i] = fmaf(d * d, w4[e], rsum[i]);
           if (dp && ok) dp[e] = d;
+          if (ph && ok) {
+            const bf16 dh = (bf16)d;
+            ph[e] = dh;
+            pl[e] = (bf16)(d - (float)dh);
+          }
         }
       }
       if (ar.o_hi) {
@@ -261,6 +273,10 @@ int mmad_gemm_x3_dispatch(int epi, const void* A, int lda, const void* B, int ld
   MMAD_CHECK_ARG(ep_in.out || epi == GEMM_EPI_SCORE, "gemm x3: null output");
   MMAD_CHECK_ARG(!ep_in.out || ep_in.ldo % 4 == 0, "gemm x3: ldo must be a multiple of 4");
   MMAD_CHECK_ARG(!ep_in.out32 || (ep_in.ld32 % 4 == 0 && ep_in.ld32 >= Np), "gemm x3: bad ld32");
+  MMAD_CHECK_ARG((ep_in.dp_hi == nullptr) == (ep_in.dp_lo == nullptr), "gemm x3: diff planes come as a pair");
+  MMAD_CHECK_ARG(!ep_in.dp_hi || (epi == GEMM_EPI_SCORE && ep_in.dp_col >= 0 &&
+                                  ep_in.lddp >= ep_in.dp_col + ep_in.N),
+                 "gemm x3: diff planes need the score epilogue and lddp >= dp_col + N");
   GemmEpi ep = ep_in;
   X3Args ar{};
   ar.a_hi = (const bf16*)A;

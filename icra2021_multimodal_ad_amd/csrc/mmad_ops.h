@@ -12,6 +12,9 @@ int mmad_sse_partials(int dtype, int M, int N, int Np, const void* y, const floa
                       float* part, int nparts, void* stream);
 int mmad_to_bf16(int64_t n, const float* x, void* y, void* stream);
 int mmad_from_bf16(int64_t n, const void* x, float* y, void* stream);
+// zero the padding of `planes` packed [Mp][Kp] matrices of esize-byte elements
+// (2 or 4) that follow each other: columns >= K of rows < M and rows >= M whole
+int mmad_zero_pad(int esize, int planes, int M, int K, int Mp, int Kp, void* x, void* stream);
 int64_t mmad_vib_kl_parts(int B, int k, int ld_z);
 // as the C-ABI forms, with the per-call values read from `dyn` (nullable)
 int mmad_pack_input_dyn(int dtype, int M, int K, int Mp, int Kp, const float* x, int ld_x,

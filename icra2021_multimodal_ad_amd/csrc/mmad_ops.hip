@@ -1341,6 +1341,27 @@ int mmad_split_planes(int64_t n, const float* src, void* hi, void* lo, void* str
   return MMAD_OK;
 }
 
+// one block per row of one plane: columns >= K of a valid row, the whole row from M on
+template <typename T>
+__global__ __launch_bounds__(256) void zero_pad_k(int M, int K, int Mp, int Kp, T* __restrict__ x) {
+  const int row = blockIdx.x;
+  T* p = x + ((size_t)blockIdx.y * Mp + row) * Kp;
+  for (int c = (row < M ? K : 0) + threadIdx.x; c < Kp; c += 256) p[c] = (T)0.f;
+}
+
+int mmad_zero_pad(int esize, int planes, int M, int K, int Mp, int Kp, void* x, void* stream) {
+  MMAD_CHECK_ARG(x && (esize == 2 || esize == 4) && planes >= 1 && M >= 0 && K >= 0 && M <= Mp && K <= Kp,
+                 "zero_pad: bad arguments");
+  if (M == Mp && K == Kp) return MMAD_OK;
+  const dim3 grid(Mp, planes);
+  if (esize == 2)
+    zero_pad_k<bf16><<<grid, 256, 0, (hipStream_t)stream>>>(M, K, Mp, Kp, (bf16*)x);
+  else
+    zero_pad_k<float><<<grid, 256, 0, (hipStream_t)stream>>>(M, K, Mp, Kp, (float*)x);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
 int mmad_from_bf16(int64_t n, const void* x, float* y, void* stream) {
   if (n == 0) return MMAD_OK;
   from_bf16_k<<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(n, (const bf16*)x, y);

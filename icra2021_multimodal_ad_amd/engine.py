@@ -58,6 +58,7 @@ class NativeAE:
         self._synced_version = None
         self._score_precision = None   # set_score_precision: None or "bf16x3"
         self._planes = None
+        self._nap = None               # set_nap: the attached fit's tensors (kept alive here)
         # version of the fp32 master as the plugin surface sees it: the
         # reference-shaped nn.Parameters are views with their OWN version
         # counters (load_state_dict / a torch optimizer bump those, not
@@ -105,6 +106,10 @@ class NativeAE:
             if self._planes is None or self._planes.device != self.device:
                 self._planes = torch.zeros(2 * self.n_weight, device=self.device, dtype=torch.bfloat16)
             call("mmad_ae_set_score_planes", self._h, ptr(self._planes))
+        if getattr(self, "_nap", None) is not None:
+            # a NAP fit lives on one device and names score planes that may be gone
+            self._nap = None
+            call("mmad_ae_set_nap", self._h, 0, 0, 0, None, None, None, _native.F32, None, None)
         if getattr(self, "_grad_bf16", None) is not None:
             # the bf16 exchange scratch follows the buffers to their new device
             self.set_grad_bf16(True)
@@ -141,6 +146,8 @@ class NativeAE:
         if precision is not None and self.dt != _native.F32:
             raise ValueError("score precision 'bf16x3' is for fp32 models (a bf16 model scores on "
                              "its own shadow)")
+        if self._nap is not None:
+            self.set_nap(None)         # an attached fit names the precision it was attached under
         self._score_precision = precision
         self._synced_version = None
         self._ws = None            # the workspace size depends on it
@@ -150,6 +157,45 @@ class NativeAE:
                 call("mmad_ae_set_score_planes", self._h, None)
         elif self.device.type == "cuda":
             self._bind()
+
+    def set_nap(self, fit, start=0, end=None, precision="f32"):
+        """Attach a NAP fit to the scoring passes (mmad_ae_set_nap): ``fit`` =
+        (R, vt [Rp, Kp], bias [Rp], w [Rp]) fp32 on this device, as NapScorer
+        lays them out, over the diff layers [start, end); ``precision`` = the
+        NAP GEMM's, "f32" (exact) or "bf16x3" (needs
+        set_score_precision("bf16x3")).  ``score(..., nap_out=)`` and
+        ``score_stream(..., nap_out=)`` then also write the per-window NAP
+        scores.  The tensors are read when a pass runs (re-fitting them in
+        place is seen; "bf16x3" splits vt once, here).  ``None`` detaches."""
+        if fit is None:
+            self._nap = None
+            if self.device.type == "cuda":
+                call("mmad_ae_set_nap", self._h, 0, 0, 0, None, None, None, _native.F32, None, None)
+            return
+        if precision not in ("f32", "bf16x3"):
+            raise ValueError(f"NAP precision {precision!r}: expected 'f32' or 'bf16x3'")
+        R, vt, bias, w = fit
+        end = self.n_enc + 1 if end is None else int(end)
+        for t in (vt, bias, w):
+            self._require(t)
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("set_nap: vt / bias / w must be contiguous fp32 tensors")
+        W = sum(self.diff_widths()[int(start):end])
+        if tuple(vt.shape) != (_native.pad(R), _native.pad(W)) or bias.numel() != vt.shape[0] \
+                or w.numel() != vt.shape[0]:
+            raise ValueError(f"set_nap: fit shapes {tuple(vt.shape)} do not match R={R}, W={W}")
+        x3 = precision == "bf16x3"
+        planes = torch.empty((2,) + tuple(vt.shape), device=self.device, dtype=torch.bfloat16) if x3 else None
+        call("mmad_ae_set_nap", self._h, int(start), end, int(R), ptr(vt), ptr(bias), ptr(w),
+             _native.BF16X3 if x3 else _native.F32, ptr(planes), stream_ptr())
+        self._nap = (vt, bias, w, planes)
+
+    def nap_operand(self, B):
+        """(byte offset in the aligned workspace, Mp, Kp, W, dtype) of the packed
+        NAP operand for a batch of B windows (mmad_ae_nap_operand)."""
+        info = (ctypes.c_int64 * 5)()
+        call("mmad_ae_nap_operand", self._h, int(B), info)
+        return tuple(int(v) for v in info)
 
     @property
     def score_dtype(self):
@@ -374,9 +420,11 @@ class NativeAE:
              self.dec_widths[-1], ptr(loss), ws, nb, stream_ptr())
         return xh, loss
 
-    def score(self, x, want_diffs=False):
+    def score(self, x, want_diffs=False, nap_out=None):
         """Per-window squared-diff sums [n_enc+1, B] (and the concatenated diffs
-        [B, sum widths] if asked) -- reconstruction_aggregation.get_diffs."""
+        [B, sum widths] if asked) -- reconstruction_aggregation.get_diffs.
+        nap_out (fp32 [>=B], with a fit attached by set_nap): also the NAP
+        scores, from the same pass (mmad_ae_score_nap)."""
         self._require(x)
         x = self._as_input(x, self.enc_widths[0])
         B = x.shape[0]
@@ -387,14 +435,28 @@ class NativeAE:
         if want_diffs:
             diffs = torch.empty((B, self.diff_width()), device=self.device)
         self.gen += 1
+        if nap_out is not None:
+            if want_diffs:
+                raise ValueError("score: nap_out and want_diffs exclude each other")
+            self._check_nap_out(nap_out, B)
+            call("mmad_ae_score_nap", self._h, ptr(x), x.stride(0), B, ptr(lsq), ptr(nap_out), ws, nb,
+                 stream_ptr())
+            return lsq, None
         call("mmad_ae_score", self._h, ptr(x), x.stride(0), B, ptr(lsq), ptr(diffs), ws, nb,
              stream_ptr())
         return lsq, diffs
 
-    def score_stream(self, x, batch, out, graph=True):
+    def _check_nap_out(self, nap_out, n):
+        if nap_out.device != self.device or nap_out.dtype != torch.float32 or nap_out.dim() != 1 \
+                or nap_out.stride(0) != 1 or nap_out.shape[0] < n:
+            raise ValueError("nap_out must be a contiguous fp32 [>=N] tensor on the model device")
+
+    def score_stream(self, x, batch, out, graph=True, nap_out=None):
         """Whole-dataset scoring pass (mmad_ae_score_stream): x [N, D] fp32 on
         this device, out [n_enc+1, >=N] fp32 with unit column stride.  With
-        graph=True the pass is captured once and replayed as one hipGraph."""
+        graph=True the pass is captured once and replayed as one hipGraph.
+        nap_out (fp32 [>=N], with a fit attached by set_nap): the pass also
+        writes the NAP scores (mmad_ae_score_nap_stream)."""
         self._require(x)
         x = self._as_input(x, self.enc_widths[0])
         N = x.shape[0]
@@ -405,6 +467,11 @@ class NativeAE:
         B = min(int(batch), N)
         ws, nb = self.workspace(B, 1)
         self.gen += 1
+        if nap_out is not None:
+            self._check_nap_out(nap_out, N)
+            call("mmad_ae_score_nap_stream", self._h, ptr(x), x.stride(0), N, B, ptr(out),
+                 out.stride(0), ptr(nap_out), ws, nb, 1 if graph else 0, stream_ptr())
+            return out
         call("mmad_ae_score_stream", self._h, ptr(x), x.stride(0), N, B, ptr(out), out.stride(0),
              ws, nb, 1 if graph else 0, stream_ptr())
         return out

@@ -50,6 +50,14 @@ def _device_diffs(model, x, batch_size):
     return torch.cat(parts, dim=0)
 
 
+def _stream_nap(model, x, batch_size, nap):
+    """NAP scores [N] of x from the fused scoring pass (``nap`` attached to model)."""
+    x = x.to(model._native.device).float().contiguous()
+    _, scores = score_windows(x, model, batch_size=batch_size, graph=False, nap=nap)
+    model._native.check_status()
+    return scores
+
+
 def _nap_model(model, cfg):
     """The model whose diffs NAP consumes.  NAP standardises every principal
     component of the train diffs by its variance (utils/normalize.py:36-45,
@@ -108,7 +116,8 @@ class NoveltyDetecter:
             out["sap"] = (sap_from_layer_sq(lv, widths, start, end), sap_from_layer_sq(lt, widths, start, end))
             nap = NapScorer(model, start_layer_index=start, end_layer_index=end)
             cuts = np.cumsum([0] + widths)
-            sel = slice(int(cuts[nap.sel.start]), int(cuts[min(nap.sel.stop, n)]))
+            nap_sel = nap.sel
+            sel = slice(int(cuts[nap_sel.start]), int(cuts[min(nap_sel.stop, n)]))
             nm = _nap_model(model, cfg)
             nap_train = rows(lambda v: _device_diffs(nm, v, cfg.batch_size)[:, sel].contiguous(), train_x)
             path = getattr(cfg, "train_diffs", None)
@@ -116,8 +125,17 @@ class NoveltyDetecter:
                 torch.save(nap_train.cpu(), path)           # utils/metric.py:205
             nap = NapScorer.standalone(nap_train.shape[1], device=nat.device).fit(train_diffs=nap_train)
             del nap_train
-            out["nap"] = (rows(lambda v: nap.score(_device_diffs(nm, v, 698)[:, sel]), valid_x),
-                          rows(lambda v: nap.score(_device_diffs(nm, v, 698)[:, sel]), test_x))
+            if getattr(cfg, "nap_stream", False):
+                # opt-in: valid / test NAP from the fused scoring pass (the diffs
+                # stay in the workspace); config.nap_precision picks the NAP GEMM
+                nap.attach(nm, precision=getattr(cfg, "nap_precision", "f32"),
+                           layers=(nap_sel.start, min(nap_sel.stop, n)))
+                out["nap"] = (rows(lambda v: _stream_nap(nm, v, 698, nap), valid_x),
+                              rows(lambda v: _stream_nap(nm, v, 698, nap), test_x))
+                nap.detach()
+            else:
+                out["nap"] = (rows(lambda v: nap.score(_device_diffs(nm, v, 698)[:, sel]), valid_x),
+                              rows(lambda v: nap.score(_device_diffs(nm, v, 698)[:, sel]), test_x))
             del nm
         return out
 

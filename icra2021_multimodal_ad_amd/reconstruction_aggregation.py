@@ -35,26 +35,34 @@ def get_diffs(x, model, batch_size=698):
     return [np.concatenate(o, axis=0) for o in out]
 
 
-def score_windows(x, model, batch_size=65536, out=None, graph=True):
+def score_windows(x, model, batch_size=65536, out=None, graph=True, nap=None, nap_out=None):
     """Per-window sum of squared diffs per layer, [n_enc+1, N] fp32 on the
     device.  x: [N, D] tensor.  Resident on the model's device: ONE native call
     for the whole pass (mmad_ae_score_stream), replayed as a captured hipGraph
-    from the second call on (graph=True); elsewhere: streamed in batches."""
+    from the second call on (graph=True); elsewhere: streamed in batches.
+    nap: a NapScorer attached to this model (NapScorer.attach) -- the same pass
+    also produces the NAP scores and (layer_sq, nap_scores [N]) is returned."""
     model.eval()
     dev = _device_of(model)
     n = x.shape[0]
     nl = model._native.n_enc + 1
     if out is None:
         out = torch.empty((nl, n), device=dev)
+    if nap is not None:
+        if nap.attached_to is not model:
+            raise ValueError("score_windows: attach the NapScorer to this model first (NapScorer.attach)")
+        if nap_out is None:
+            nap_out = torch.empty(n, device=dev)
     with torch.no_grad():
         if x.device == dev and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 \
                 and out.stride(1) == 1:
-            return model._native.score_stream(x, batch_size, out, graph=graph)
+            model._native.score_stream(x, batch_size, out, graph=graph, nap_out=nap_out)
+            return out if nap is None else (out, nap_out)
         for s in range(0, n, batch_size):
             xb = x[s:s + batch_size].to(dev, non_blocking=True)
-            lsq, _ = model._native.score(xb)
+            lsq, _ = model._native.score(xb, nap_out=None if nap is None else nap_out[s:])
             out[:, s:s + xb.shape[0]] = lsq
-    return out
+    return out if nap is None else (out, nap_out)
 
 
 def base_from_layer_sq(layer_sq, widths):
@@ -138,6 +146,33 @@ class NapScorer:
         cuts = np.cumsum([0] + list(widths))
         self.c0, self.c1 = int(cuts[self.sel.start]), int(cuts[min(self.sel.stop, n)])
         self.fit_state = None
+        self.attached_to = None
+
+    def attach(self, model, precision="f32", layers=None):
+        """Put this fit into ``model``'s scoring passes (NativeAE.set_nap):
+        ``score_windows(x, model, nap=self)`` then returns the NAP scores with
+        the layer sums, the diffs never leaving the workspace.  precision: the
+        NAP GEMM's -- "f32" (exact, the default) or "bf16x3" (split-bf16 on the
+        bf16 matrix cores; the model must score in "bf16x3" too).  The scorer
+        must cover the same layer range of the same diff widths it was built
+        for."""
+        W, R, Kp, Rp, vt, bias, w = self._dev
+        nat = model._native
+        widths = nat.diff_widths()
+        start, stop = self.sel.start, min(self.sel.stop, len(widths))
+        if layers is not None:                     # a standalone scorer: name the layers it was fit on
+            start, stop = int(layers[0]), int(layers[1])
+        if sum(widths[start:stop]) != W:
+            raise ValueError(f"NapScorer.attach: fit width {W} != the model's layers [{start}, {stop})")
+        self.detach()
+        nat.set_nap((R, vt, bias, w), start, stop, precision)
+        self.attached_to = model
+        return self
+
+    def detach(self):
+        if self.attached_to is not None:
+            self.attached_to._native.set_nap(None)
+            self.attached_to = None
 
     @classmethod
     def standalone(cls, width, device=None):
@@ -173,10 +208,14 @@ class NapScorer:
         self._dev = (W, R, Kp, Rp, vt, bias, w)
         return self
 
-    def score(self, diffs):
+    def score(self, diffs, precision="f32"):
         """diffs: list of per-layer arrays or [N, W] (host or device) -> [N]
-        NAP scores (device fp32)."""
-        from ._native import call, ptr, stream_ptr, pad, F32, require_gpu
+        NAP scores (device fp32).  precision "bf16x3": diffs and V^T as
+        split-bf16 planes, the GEMM on the bf16 matrix cores (explicit opt-in;
+        the default stays the exact-fp32 GEMM)."""
+        from ._native import call, ptr, stream_ptr, pad, F32, BF16X3, require_gpu
+        if precision not in ("f32", "bf16x3"):
+            raise ValueError(f"NAP precision {precision!r}: expected 'f32' or 'bf16x3'")
         W, R, Kp, Rp, vt, bias, w = self._dev
         x = self._cat(diffs).to(self.device, torch.float32).contiguous()
         require_gpu(x)
@@ -186,6 +225,12 @@ class NapScorer:
         xp = torch.empty((Mp, Kp), device=self.device, dtype=torch.float32)
         dt = F32
         s = stream_ptr()
+        if precision == "bf16x3":
+            dt = BF16X3                            # planes fill an fp32 matrix's bytes
+            n = Rp * Kp
+            vtp = torch.empty(2 * n, device=self.device, dtype=torch.bfloat16)
+            call("mmad_split_planes", n, ptr(vt), ptr(vtp), ptr(vtp[n:]), s)
+            vt = vtp
         call("mmad_pack_input", dt, N, W, Mp, Kp, ptr(x), x.stride(0), ptr(xp), s)
         rowsq = torch.empty((Rp // 128, Mp), device=self.device)
         out = torch.empty(N, device=self.device)

@@ -25,8 +25,8 @@
  *    it stands for float(hi) + float(lo).  GEMMs form hi.hi + (hi.lo + lo.hi)
  *    on the bf16 matrix cores with fp32 accumulation (fp32-class results at
  *    three bf16 MFMAs per step).  Accepted by mmad_pack_input,
- *    mmad_unpack_output, mmad_fc_fwd (stats == NULL), mmad_fc_fwd_score and
- *    mmad_vib_reparam_fwd (deterministic); every other operator returns
+ *    mmad_unpack_output, mmad_fc_fwd (stats == NULL), mmad_fc_fwd_score,
+ *    mmad_nap_score and mmad_vib_reparam_fwd (deterministic); every other operator returns
  *    MMAD_EUNSUPPORTED for it and launches nothing.
  *  - Every call returns 0 (MMAD_OK) or a negative status; the message is in
  *    mmad_last_error_string() (thread-local).  No exceptions cross the ABI.
@@ -217,7 +217,9 @@ int mmad_bn_train_apply(int dtype, int M, int N, int Mp, int Np, const void* a,
  *   score[m] = (1/R) sum_{j<R} w[j] * (sum_k x[m][k] vt[j][k] + bias[j])^2
  * with vt = V^T of the rotation, bias = -(mu_r V + mu_s), w = 1/var (0 on
  * padding).  x: packed concatenated diffs [Mp][Kp] (dtype), vt [Rp][Kp]
- * (dtype); rowsq: fp32 workspace [Rp/128][Mp]; score fp32 [M]. */
+ * (dtype); rowsq: fp32 workspace [Rp/128][Mp]; score fp32 [M].
+ * MMAD_BF16X3: x is planes [2][Mp][Kp] and vt planes [2][Rp][Kp]
+ * (mmad_pack_input / mmad_split_planes); bias and w stay fp32. */
 int mmad_nap_score(int dtype, int M, int K, int R, int Mp, int Kp, int Rp, const void* x,
                    const void* vt, const float* bias, const float* w, float* rowsq, float* score,
                    void* stream);
@@ -572,6 +574,50 @@ int mmad_ae_score(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq, 
 int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch,
                          float* layer_sq, int64_t ld_sq, void* ws, int64_t ws_bytes, int use_graph,
                          void* stream);
+/* Streamed NAP: the NAP score of every window from the scoring pass itself.
+ * mmad_ae_set_nap attaches a fit over the concatenated diffs of the diff
+ * layers [start, end) (0 = x_hat - x, 1 + e = encoder layer e; 0 <= start <
+ * end <= n_enc + 1), W = the sum of their widths, Kp / Rp = W / R rounded up
+ * to the pad granule: vt fp32 [Rp][Kp] (V^T, zero padding), bias [Rp], w [Rp]
+ * as mmad_nap_score takes them, all caller-owned device buffers that must
+ * outlive the attachment and are read when a pass runs (a replayed graph
+ * included: re-fitting them in place is seen).  dtype = the NAP GEMM's:
+ *  - MMAD_F32 (exact; any handle dtype -- a bf16 handle's fp32 diffs feed it);
+ *  - MMAD_BF16X3: needs score planes attached (mmad_ae_score_dtype ==
+ *    MMAD_BF16X3, else MMAD_EINVAL and nothing is launched) and vt_planes,
+ *    bf16 [2][Rp][Kp], 16-byte aligned like vt, which this call fills from vt
+ *    with one mmad_split_planes launch on `stream` (once: after re-fitting vt
+ *    in place, attach again).  vt_planes is ignored for MMAD_F32.
+ * vt == NULL detaches.  While a fit is attached mmad_ae_workspace_bytes grows
+ * by the packed NAP operand [Mp][Kp] and the NAP GEMM's row partials, carved
+ * after every other buffer (no other offset moves); attaching or detaching
+ * drops the cached score graphs.  Every other entry point runs exactly as
+ * without a fit.
+ * mmad_ae_score_nap / mmad_ae_score_nap_stream: as mmad_ae_score (diffs ==
+ * NULL) / mmad_ae_score_stream -- the same layer_sq bits -- and nap fp32 [B] /
+ * [N] (device) = the NAP score of each window.  Per batch, in the same stream
+ * or captured graph, the score GEMMs of the layers in range write their diffs
+ * straight into the packed operand (fp32 through the diff output, planes
+ * through the x3 score epilogue's diff-plane output; its padding is zeroed
+ * for every batch), then the NAP GEMM and its column sum run as
+ * mmad_nap_score's do.  With an MMAD_F32 NAP GEMM the scores equal, bit for
+ * bit, mmad_ae_score(diffs) -> the range's columns -> mmad_pack_input ->
+ * mmad_nap_score at the same batch size.  The graph cache key also covers nap
+ * and vt.  MMAD_EINVAL (nothing launched): nap == NULL, no fit attached, or an
+ * MMAD_BF16X3 fit whose score planes were detached.
+ * mmad_ae_nap_operand (query; tests, debugging): info int64[5] = byte offset
+ * of the packed operand in a workspace carved for B windows, its rows Mp, its
+ * leading dimension Kp, W, the NAP GEMM dtype (MMAD_BF16X3: hi plane at the
+ * offset, lo plane Mp*Kp bf16 elements on). */
+int mmad_ae_set_nap(mmad_ae* h, int start, int end, int R, const float* vt, const float* bias,
+                    const float* w, int dtype, void* vt_planes, void* stream);
+int mmad_ae_score_nap(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq, float* nap,
+                      void* ws, int64_t ws_bytes, void* stream);
+int mmad_ae_score_nap_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch,
+                             float* layer_sq, int64_t ld_sq, float* nap, void* ws, int64_t ws_bytes,
+                             int use_graph, void* stream);
+int mmad_ae_nap_operand(const mmad_ae* h, int B, int64_t* info);
+
 /* Split-K health of the executor workspace `ws` (as mmad_gemm_status): a
  * no-op returning MMAD_OK unless split-K is enabled (tuning knob 4 > 1);
  * otherwise synchronises `stream` and returns MMAD_EHIP if any GEMM combine
