@@ -45,7 +45,9 @@ SIGNATURES = {
     "mmad_nap_score": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mmad_fc_bwd_data": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "mmad_fc_bwd_weight": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
-    "mmad_fc_bwd_weight_adam": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P]),
+    "mmad_fc_bwd_weight_group": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_P),
+                                      ctypes.POINTER(_P), ctypes.POINTER(_P), _P]),
+    "mmad_fc_bwd_weight_adam":(_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P]),
     "mmad_bn_act_bwd_ws": (ctypes.c_size_t, [_I, _I]),
     "mmad_bn_act_bwd": (_I, [_I, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                              _P]),
@@ -71,6 +73,9 @@ SIGNATURES = {
     "mmad_ae_bind": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "mmad_ae_sync_shadow": (_I, [_P, _P]),
     "mmad_ae_set_shadow_pair": (_I, [_P, _P]),
+    "mmad_ae_set_dw_group": (_I, [_P, _I, _I]),
+    "mmad_dw_group_plan": (_I, [_I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _I,
+                                _I, _I, ctypes.POINTER(_I)]),
     "mmad_ae_set_score_planes": (_I, [_P, _P]),
     "mmad_ae_score_dtype": (_I, [_P]),
     "mmad_ae_current_shadow": (_P, [_P]),
@@ -139,8 +144,10 @@ KNOB = dict(tile=0, group_m=1, autotune=2, dbg=3, splitk=4, tile_adam=5, tile_bw
             splitk_dw_f32_blocks=32)
 # host-side schedule choices of the Python executor wrapper (engine.py), read
 # when a model is built: a second bf16 weight shadow (ping-pong), and whether
-# train_step replays one captured hipGraph per step instead of the eager enqueue
-SCHEDULE = {"shadow_pair": True, "train_graph": False}
+# train_step replays one captured hipGraph per step instead of the eager enqueue;
+# dw_group / dw_group_members: the block budget and member cap of the ping-pong
+# step's grouped dW launches (mmad_ae_set_dw_group; None = the library's default)
+SCHEDULE = {"shadow_pair": True, "train_graph": False, "dw_group": None, "dw_group_members": None}
 
 
 def tune_get(name):

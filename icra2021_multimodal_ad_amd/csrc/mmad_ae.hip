@@ -143,6 +143,15 @@ struct mmad_ae {
   // by more than a layer anyway, each fork saved is a ~5-us hold on the
   // main stream; 0 = every layer forks)
   int fork_pair_below = 0;
+  // ping-pong steps (mmad_ae_set_dw_group): consecutive side-stream layers
+  // whose dW + Adam GEMM takes the 64x64 tile are issued as ONE grouped launch
+  // (mmad_gemm_dispatch_group) at the lowest member's fork -- at 4096 rows
+  // each of the narrow layers' launches is one block's 64-stage K loop,
+  // 23-25 us for 16 to 135 blocks, and they ran back to back.  blocks = the
+  // group's budget of padded blocks (0 = off: every dW its own launch; < 0 =
+  // one resident round of the kernel), members = at most this many per group
+  int dw_group_blocks = MMAD_DW_GROUP_BLOCKS_DEFAULT;
+  int dw_group_members = MMAD_GEMM_GROUP_MAX;
   hipEvent_t ev_hold = nullptr;
   // fused step: dW GEMMs of layers < dw_main run on the caller's stream
   // (knob 19; tools/sched_sweep.py: 0.499 ms (2) vs 0.512 (1) vs 0.523 (3));
@@ -820,6 +829,93 @@ static int ae_gemm(const mmad_ae* h, const AeWS& w, int dt, int epi, const void*
   return MMAD_OK;
 }
 
+// Which side-stream dW + Adam GEMMs share a grouped launch.  Layers l_hi - 1
+// down to l_lo are visited in backward order; consecutive layers the tile
+// rule (mmad_tile_adam_for) puts on the 64x64 tile, with at most budget / 2
+// padded blocks each, join the open group while it stays within `budget`
+// padded blocks and `members` members; any other layer, or one that would not
+// fit, closes it.  group_of[l] = the group's
+// index (in launch order), or -1 for a layer with a launch of its own (a group
+// of one is the ordinary launch).  Returns the number of groups.  A function
+// of its arguments and knob 5 only.
+int mmad_dw_group_plan(int n_layers, const int* Np, const int* Kp, const int* rows, int l_lo, int l_hi,
+                       int budget, int members, int* group_of) {
+  if (n_layers <= 0 || !Np || !Kp || !rows || !group_of) return 0;
+  for (int l = 0; l < n_layers; ++l) group_of[l] = -1;
+  if (members > MMAD_GEMM_GROUP_MAX) members = MMAD_GEMM_GROUP_MAX;
+  if (budget <= 0 || members < 2) return 0;
+  int groups = 0, first = -1, count = 0, blocks = 0;
+  auto close = [&]() {
+    if (count >= 2) {
+      for (int m = first; m > first - count; --m) group_of[m] = groups;
+      ++groups;
+    }
+    first = -1;
+    count = blocks = 0;
+  };
+  for (int l = (l_hi < n_layers ? l_hi : n_layers) - 1; l >= (l_lo > 0 ? l_lo : 0); --l) {
+    const bool fits_tile = Np[l] > 0 && Kp[l] > 0 && Np[l] % 64 == 0 && Kp[l] % 64 == 0 &&
+                           mmad_tile_adam_for(Np[l], Kp[l], rows[l]) == 3;
+    const int bl = fits_tile ? mmad_gemm_group_blocks(Np[l], Kp[l]) : 0;
+    // a member takes at most half the budget: with the budget at one resident
+    // round (two blocks per CU) a larger launch has a block on every CU and is
+    // bound by throughput, not by one block's latency -- held back for a
+    // group it would only start later (c3: layer 7, 280 blocks; layer 2, 352)
+    if (!fits_tile || 2 * bl > budget) {
+      close();
+      continue;
+    }
+    if (count == members || blocks + bl > budget) close();
+    if (count == 0) first = l;
+    ++count;
+    blocks += bl;
+  }
+  close();
+  return groups;
+}
+
+// a side-stream dW GEMM of the backward waiting to be issued (run_backward)
+struct PendingDW {
+  const void *dz, *in;
+  int lda, ldb, M, N, K;
+  GemmEpi ep;
+  int layer;
+};
+
+// the grouped form of ae_gemm for `n` deferred side-stream dW GEMMs: one
+// launch, or MMAD_GEMM_GROUP_REFUSED with nothing launched.  The probe of any
+// member's PROBE_DW id brackets the whole launch; the mask names every member.
+static int ae_gemm_group(const mmad_ae* h, const AeWS& w, int dt, const PendingDW* q, int n, hipStream_t s) {
+  if (n > MMAD_GEMM_GROUP_MAX) return MMAD_GEMM_GROUP_REFUSED;
+  const int r = (h->side && s == h->side) ? 1 : 0;
+  GemmGroupProblem gp[MMAD_GEMM_GROUP_MAX];
+  unsigned mask = 0;
+  bool hit = false;
+  for (int i = 0; i < n; ++i) {
+    gp[i] = GemmGroupProblem{q[i].dz, q[i].in, q[i].lda, q[i].ldb, q[i].M, q[i].N, q[i].K, q[i].ep};
+    gp[i].ep.sk_slab = w.sk_slab[r];
+    gp[i].ep.sk_ctl = w.sk_ctl[r];
+    mask |= 1u << (q[i].layer % 32);
+    hit = hit || PROBE_DW + q[i].layer == h->probe_id;
+  }
+  const bool rec = hit && !h->capturing && 2 * h->probe_n < (int)h->probe_ev.size();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (rec && h->probe_kev) {
+    e0 = h->probe_ev[2 * h->probe_n];
+    e1 = h->probe_ev[2 * h->probe_n + 1];
+  } else if (rec) {
+    MMAD_HIP_CHECK(hipEventRecord(h->probe_ev[2 * h->probe_n], s));
+  }
+  const int rc = mmad_gemm_dispatch_group(dt, n, gp, s, e1, e0);
+  if (rc != MMAD_OK) return rc;
+  if (rec) {
+    if (!h->probe_kev) MMAD_HIP_CHECK(hipEventRecord(h->probe_ev[2 * h->probe_n + 1], s));
+    ++h->probe_n;
+    h->probe_mask = mask;
+  }
+  return MMAD_OK;
+}
+
 static inline int rows_of(const AeWS& w, const AeLayer& a) { return a.enc ? w.B : w.B * w.k; }
 static inline int prows_of(const AeWS& w, const AeLayer& a) { return a.enc ? w.Mpe : w.Mpd; }
 static float* running_mean(const mmad_ae* h, const AeLayer& a) { return h->running + a.bn_off; }
@@ -972,13 +1068,6 @@ using AdamHyper = MmadAdamConsts;   // w1 = float(1 - beta1), w2 = float(1 - bet
 // partials come from the MSE-fused forward epilogue; otherwise the caller has
 // packed dL/dx_hat into the last layer's dy buffer.  adam != null: each
 // layer's Adam update runs on the side stream right after its dW GEMM.
-struct PendingDW {
-  const void *dz, *in;
-  int lda, ldb, M, N, K;
-  GemmEpi ep;
-  int layer;
-};
-
 static int finish_reductions(mmad_ae* h, AeWS& w, bool biases, bool from_mse, float beta_kl,
                              float* loss_out, hipStream_t st);
 
@@ -997,7 +1086,48 @@ static int run_backward(mmad_ae* h, AeWS& w, bool from_mse, float beta_kl, const
   std::vector<char> fork_done(nL, 0);
   const bool fork_kev = h->fork_on_kernel && !h->capturing;
   // does layer l's side-stream dW (ping) get a fork event of its own (knob 35)?
+  // grouped dW launches (single-GPU ping-pong step only): grp[l] = the group
+  // layer l's dW + Adam GEMM is issued with, -1 = a launch of its own
+  std::vector<int> grp(nL, -1);
+  if (adam && !h->comm && w.ping && !h->capturing && !h->side_hold && h->dw_group_blocks != 0) {
+    std::vector<int> np(nL), kp(nL), rows(nL);
+    for (int l = 0; l < nL; ++l) {
+      np[l] = h->L[l].Np;
+      kp[l] = h->L[l].Kp;
+      rows[l] = prows_of(w, h->L[l]);
+    }
+    const int budget = h->dw_group_blocks < 0 ? mmad_gemm_group_capacity(dt) : h->dw_group_blocks;
+    mmad_dw_group_plan(nL, np.data(), kp.data(), rows.data(), w.dw_main, nL - h->dw_late, budget,
+                       h->dw_group_members, grp.data());
+  }
+  // issue the deferred side-stream dW GEMMs, then `cur`: members of one group
+  // (adjacent in issue order) as one launch, every other -- and a group the
+  // dispatcher refuses -- as its own
+  auto issue_side = [&](const PendingDW& cur) -> int {
+    pending.push_back(cur);
+    for (size_t i = 0; i < pending.size();) {
+      const int gid = grp[pending[i].layer];
+      size_t j = i + 1;
+      while (gid >= 0 && j < pending.size() && grp[pending[j].layer] == gid) ++j;
+      int rc = MMAD_GEMM_GROUP_REFUSED;
+      if (j - i >= 2) rc = ae_gemm_group(h, w, dt, &pending[i], (int)(j - i), side);
+      if (rc == MMAD_GEMM_GROUP_REFUSED) {
+        for (size_t m = i; m < j; ++m) {
+          const PendingDW& q = pending[m];
+          RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, q.dz, q.lda, q.in, q.ldb, q.M, q.N, q.K, q.ep,
+                         side, nullptr, PROBE_DW + q.layer));
+        }
+      } else if (rc != MMAD_OK) {
+        return rc;
+      }
+      i = j;
+    }
+    pending.clear();
+    return MMAD_OK;
+  };
   auto fork_ev = [&](int l) {
+    // a group forks once, at its lowest member
+    if (grp[l] >= 0) return l == 0 || grp[l - 1] != grp[l];
     const int P = h->fork_pair_below;
     if (P <= 0 || l > P || l == w.dw_main) return true;
     return (P - l) % 2 == 1;
@@ -1284,12 +1414,7 @@ static int run_backward(mmad_ae* h, AeWS& w, bool from_mse, float beta_kl, const
       } else if (ping) {
         if (late) MMAD_HIP_CHECK(hipEventRecord(h->ev_fork[l], st));
         if (!fork_none) MMAD_HIP_CHECK(hipStreamWaitEvent(side, h->ev_fork[l], 0));
-        for (const PendingDW& q : pending)
-          RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, q.dz, q.lda, q.in, q.ldb, q.M, q.N, q.K, q.ep,
-                         side, nullptr, PROBE_DW + q.layer));
-        pending.clear();
-        RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, dz, a.Np, in, a.Kp, a.Np, a.Kp, Mp, dwe, side,
-                       nullptr, PROBE_DW + l));
+        RET_IF(issue_side(PendingDW{dz, in, a.Np, a.Kp, a.Np, a.Kp, Mp, dwe, l}));
       } else if (!rec) {
         pending.push_back(PendingDW{dz, in, a.Np, a.Kp, a.Np, a.Kp, Mp, dwe, l});
       } else {
@@ -1946,6 +2071,16 @@ int mmad_ae_probe(mmad_ae* h, int kind, int layer, int capacity) {
 }
 
 int mmad_ae_probe_layers(const mmad_ae* h) { return h ? (int)h->probe_mask : -1; }
+
+int mmad_ae_set_dw_group(mmad_ae* h, int blocks, int members) {
+  if (!h) {
+    mmad_set_error("ae_set_dw_group: null handle");
+    return MMAD_EINVAL;
+  }
+  if (blocks >= -1) h->dw_group_blocks = blocks;
+  if (members > 0) h->dw_group_members = members;
+  return MMAD_OK;
+}
 
 int mmad_ae_probe_read(mmad_ae* h, float* ms, int max_n) {
   if (!h || !ms || max_n < 0) {

@@ -306,6 +306,28 @@ int mmad_fc_bwd_weight(int dtype, int Mp, int Np, int Kp, const void* dz, const 
   return layer_gemm(dtype, GEMM_EPI_BWD_WEIGHT, dz, Np, x, Kp, Np, Kp, Mp, ep, stream);
 }
 
+int mmad_fc_bwd_weight_group(int dtype, int n, int Mp, const int* Np, const int* Kp, const void* const* dz,
+                             const void* const* x, float* const* dw, void* stream) {
+  RET_IF(check_dtype(dtype, "fc_bwd_weight_group"));
+  MMAD_CHECK_ARG(n >= 1 && n <= MMAD_GEMM_GROUP_MAX && Np && Kp && dz && x && dw,
+                 "fc_bwd_weight_group: 1 to %d problems", MMAD_GEMM_GROUP_MAX);
+  GemmGroupProblem gp[MMAD_GEMM_GROUP_MAX];
+  for (int i = 0; i < n; ++i) {
+    RET_IF(check_dims("fc_bwd_weight_group", Mp, Np[i], Kp[i], Mp, Np[i], Kp[i]));
+    MMAD_CHECK_ARG(dz[i] && x[i] && dw[i], "fc_bwd_weight_group: null operand");
+    GemmEpi ep{};
+    ep.M = Np[i]; ep.N = Kp[i]; ep.out = dw[i]; ep.ldo = Kp[i];
+    ep.tile_force = 3 + 1;   // the grouped kernel's tile; no split-K workspace: never split
+    gp[i] = GemmGroupProblem{dz[i], x[i], Np[i], Kp[i], Np[i], Kp[i], Mp, ep};
+  }
+  const int rc = mmad_gemm_dispatch_group(dtype, n, gp, (hipStream_t)stream);
+  if (rc == MMAD_GEMM_GROUP_REFUSED) {
+    mmad_set_error("fc_bwd_weight_group: the problems do not fit one grouped launch");
+    return MMAD_EUNSUPPORTED;
+  }
+  return rc;
+}
+
 int mmad_fc_bwd_weight_adam(int dtype, int Mp, int Np, int Kp, const void* dz, const void* x,
                             float* p, float* m, float* v, void* shadow, float* dw, float beta1,
                             float beta2, float eps, float step_size, float bc2_sqrt, void* stream) {

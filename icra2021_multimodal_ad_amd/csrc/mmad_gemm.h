@@ -226,6 +226,51 @@ bool mmad_gemm_bn_fusable(int dtype, int epi, int Mp, int Np);
 int mmad_gemm_x3_dispatch(int epi, const void* A, int lda, const void* B, int ldb, int Mp, int Np,
                           int K, const GemmEpi& ep, hipStream_t s);
 
+// ---- grouped dW launch: up to MMAD_GEMM_GROUP_MAX dW (+ Adam) GEMMs of the
+// 64x64 tile in ONE launch.  The narrow layers' dW GEMMs (a few dozen tiles,
+// a 64-stage K loop each at 4096 rows) are bound by one block's latency, not
+// by throughput; side by side in one grid they cost about the slowest
+// member's time instead of the sum.  Every output tile runs gemm_body exactly
+// as in its stand-alone launch (same block index, block count, tile order, K
+// order), so the bits are the separate launches'.
+#define MMAD_GEMM_GROUP_MAX 4
+// one member as the caller states it
+struct GemmGroupProblem {
+  const void *A, *B;
+  int lda, ldb;
+  int Mp, Np, K;
+  GemmEpi ep;          // done_ev / start_ev ignored (the launch's are arguments)
+};
+// one member as the kernel reads it: its block range is [first_block,
+// first_block + roundup(ntiles, 8)), so blockIdx & 7 (the XCD label the tile
+// order relies on) stays the member-local index's; blocks past ntiles idle
+struct GemmGroupEntry {
+  const void *A, *B;
+  int lda, ldb, K;
+  int first_block, ntiles;
+  GemmEpi ep;
+};
+struct GemmGroupTable {
+  int n;
+  GemmGroupEntry e[MMAD_GEMM_GROUP_MAX];
+};
+static_assert(sizeof(GemmGroupTable) <= 4096, "grouped dW launch: the table is a kernel argument");
+// padded blocks a member of Mp x Np outputs takes in a grouped launch
+inline int mmad_gemm_group_blocks(int Mp, int Np) { return ((Mp / 64) * (Np / 64) + 7) & ~7; }
+// blocks of the grouped kernel resident on the current device at once (0 if
+// unknown: no device)
+int mmad_gemm_group_capacity(int dtype);
+// Launch `n` BWD_WEIGHT problems as one grid on `s`; done_ev / start_ev
+// (nullable) ride on the launch.  Returns MMAD_OK, an error, or
+// MMAD_GEMM_GROUP_REFUSED with nothing launched -- more than
+// MMAD_GEMM_GROUP_MAX members, a split-K member, a member the tile rule
+// (mmad_tile_adam_for, a forced tile) does not put on the 64x64 tile, or more
+// padded blocks than the kernel's resident capacity: the caller then launches
+// the members separately.
+#define MMAD_GEMM_GROUP_REFUSED 1
+int mmad_gemm_dispatch_group(int dtype, int n, const GemmGroupProblem* problems, hipStream_t s,
+                             hipEvent_t done_ev = nullptr, hipEvent_t start_ev = nullptr);
+
 // cfg_used (nullable) receives the tile configuration launched
 int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B, int ldb, int Mp,
                        int Np, int K, const GemmEpi& ep, hipStream_t s, int* cfg_used = nullptr);

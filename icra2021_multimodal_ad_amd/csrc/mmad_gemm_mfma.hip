@@ -1982,6 +1982,28 @@ __global__ __launch_bounds__(Cfg<CFG>::NT, 1) void mmad_gemm_kernel_p(const T* _
   }
 }
 
+#ifndef MMAD_GEMM_B4_TU
+// Grouped dW (+ Adam) launch on the 64x64 tile (mmad_gemm_dispatch_group): the
+// block picks its problem from blockIdx.x against the members' first_block
+// (ascending; uniform over the block, so the entry is read with scalar loads
+// straight from the kernel-argument table) and runs gemm_body as block
+// v = blockIdx.x - first_block of that problem's own ntiles-block grid.
+// first_block is a multiple of 8, so v & 7 is blockIdx.x & 7.
+template <typename T>
+__global__ __launch_bounds__(Cfg<3>::NT, 1) void mmad_gemm_group_kernel(const GemmGroupTable g) {
+  const int b = blockIdx.x;
+  int i = 0;
+#pragma unroll
+  for (int j = 1; j < MMAD_GEMM_GROUP_MAX; ++j)
+    if (j < g.n && b >= g.e[j].first_block) i = j;
+  const GemmGroupEntry& e = g.e[i];
+  const int v = b - e.first_block;
+  if (v >= e.ntiles) return;   // padding block
+  gemm_body<T, float, false, false, 3, GEMM_EPI_BWD_WEIGHT>((const T*)e.A, e.lda, (const T*)e.B, e.ldb, e.K,
+                                                            e.ep, v, e.ntiles, threadIdx.x);
+}
+#endif
+
 #ifdef MMAD_GEMM_B4_TU
 // ---- the 4-wave 256x256 translation unit: tile 8's two kernels only --------
 const void* mmad_gemm_b4_kernel(int epi) {
@@ -2438,5 +2460,65 @@ int mmad_gemm_dispatch(int dtype, int epi, const void* A, int lda, const void* B
   const int run = tile_runs(cfg, p);
   if (cfg_used) *cfg_used = run;
   return launch_tile(p, run, A, lda, B, ldb, K, ep, s);
+}
+
+// ---- the grouped dW launch ------------------------------------------------
+static const void* group_kernel(int dtype) {
+  return dtype == MMAD_BF16 ? (const void*)mmad_gemm_group_kernel<bf16>
+         : dtype == MMAD_F32 ? (const void*)mmad_gemm_group_kernel<float> : nullptr;
+}
+
+int mmad_gemm_group_capacity(int dtype) { return kernel_capacity(group_kernel(dtype), TILES[3].NT); }
+
+// the tile a stand-alone dispatch of this member would take without consulting
+// the tuner (-1: it would), by mmad_gemm_dispatch's own order of precedence
+static int group_member_tile(const GemmProblem& p, const GemmEpi& ep, int K) {
+  const int cand[3] = {ep.tile_force - 1,
+                       ep.ad_p ? mmad_tile_adam_for(p.Mp, p.Np, K) : mmad_tile_epi_override(p.epi),
+                       mmad_tile_override()};
+  for (int c : cand)
+    if (tile_allowed(c, p)) return tile_runs(c, p);
+  return -1;
+}
+
+int mmad_gemm_dispatch_group(int dtype, int n, const GemmGroupProblem* problems, hipStream_t s,
+                             hipEvent_t done_ev, hipEvent_t start_ev) {
+  MMAD_CHECK_ARG(n > 0 && problems, "gemm group: empty group");
+  const void* fn = group_kernel(dtype);
+  if (n > MMAD_GEMM_GROUP_MAX || !fn) return MMAD_GEMM_GROUP_REFUSED;
+  GemmGroupTable g{};
+  g.n = n;
+  int blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const GemmGroupProblem& q = problems[i];
+    MMAD_CHECK_ARG(q.Mp > 0 && q.Np > 0 && q.K > 0 && q.Mp % 128 == 0 && q.Np % 128 == 0 && q.K % 128 == 0,
+                   "gemm group: padded dims must be multiples of 128 (Mp=%d Np=%d K=%d)", q.Mp, q.Np, q.K);
+    const int S = (q.ep.sk_slab && q.ep.sk_ctl) ? mmad_gemm_splitk(q.Mp, q.Np, q.K, dtype, GEMM_EPI_BWD_WEIGHT) : 1;
+    const GemmProblem p{dtype, GEMM_EPI_BWD_WEIGHT, q.Mp, q.Np, S, false, false, q.ep.act};
+    if (S != 1 || q.ep.bn_sync || group_member_tile(p, q.ep, q.K) != 3) return MMAD_GEMM_GROUP_REFUSED;
+    const Tile& t = TILES[3];
+    const int tiles_m = q.Mp / t.BM, tiles_n = q.Np / t.BN, ntiles = tiles_m * tiles_n;
+    GemmGroupEntry& e = g.e[i];
+    e.A = q.A;
+    e.B = q.B;
+    e.lda = q.lda;
+    e.ldb = q.ldb;
+    e.K = q.K;
+    e.first_block = blocks;
+    e.ntiles = ntiles;
+    // the member's epilogue as launch_tile would pass it
+    e.ep = q.ep;
+    e.ep.dbg = mmad_dbg_override();
+    e.ep.splitk = 1;
+    e.ep.tiles_n = tiles_n;
+    e.ep.group_m = plan_group_m(ntiles, tiles_m, t.BM, t.BN);
+    e.ep.done_ev = nullptr;
+    e.ep.start_ev = nullptr;
+    blocks += mmad_gemm_group_blocks(q.Mp, q.Np);
+  }
+  const int cap = kernel_capacity(fn, TILES[3].NT);
+  if (cap <= 0 || blocks > cap) return MMAD_GEMM_GROUP_REFUSED;
+  void* args[] = {&g};
+  return mmad_gemm_launch(fn, dim3(blocks), dim3(TILES[3].NT), s, start_ev, done_ev, args);
 }
 #endif  // MMAD_GEMM_B4_TU

@@ -39,6 +39,12 @@ class NativeAE:
              int(self.vib), float(slope), float(bn_eps), float(bn_momentum))
         self._h = h
         self._lib = lib
+        if _native.SCHEDULE["dw_group"] is not None or _native.SCHEDULE["dw_group_members"] is not None:
+            # grouped dW launches of the ping-pong step: None = the library's own default
+            blocks, members = _native.SCHEDULE["dw_group"], _native.SCHEDULE["dw_group_members"]
+            # (the setter leaves a value as it is for blocks < -1 / members <= 0)
+            call("mmad_ae_set_dw_group", h, -2 if blocks is None else int(blocks),
+                 0 if members is None else int(members))
         n_l = self.n_enc + self.n_dec
         info = (ctypes.c_int64 * (7 * n_l))()
         tot = (ctypes.c_int64 * 4)()

@@ -248,6 +248,13 @@ int mmad_fc_bwd_data(int dtype, int M, int N, int K, int Mp, int Np, int Kp, con
 int mmad_fc_bwd_weight(int dtype, int Mp, int Np, int Kp, const void* dz, const void* x,
                        float* dw, void* stream);
 
+/* n (1 to 4) such dW GEMMs over the same Mp padded rows in ONE launch of the
+ * 64x64 tile: dw[i][Np[i]][Kp[i]] = dz[i]^T . x[i], the bits of
+ * mmad_fc_bwd_weight for each.  MMAD_EUNSUPPORTED if the problems' blocks
+ * (each rounded up to 8) exceed one resident round of the kernel. */
+int mmad_fc_bwd_weight_group(int dtype, int n, int Mp, const int* Np, const int* Kp, const void* const* dz,
+                             const void* const* x, float* const* dw, void* stream);
+
 /* The standalone Activation module (modules/activation.py:20-45) on fp32
  * [M][ld] rows of N values: act = any MMAD_ACT_* (softmax / logsoftmax over
  * each row, dim=-1, max-subtracted; logsigmoid = -softplus(-x); leaky slope
@@ -413,6 +420,33 @@ int mmad_ae_score_dtype(const mmad_ae* h);
  * swap at the end of the step, so each layer's dW+Adam GEMM overlaps that
  * layer's bwd-data GEMM.  mmad_ae_sync_shadow refreshes both. */
 int mmad_ae_set_shadow_pair(mmad_ae* h, void* alt);
+
+/* Grouped dW launches of the single-GPU ping-pong step (a shadow pair set, no
+ * communicator, not graph-captured): walking the side-stream layers top-down,
+ * consecutive layers whose dW + Adam GEMM takes the 64x64 tile (knob 5's rule)
+ * are issued as ONE launch at the lowest member's fork instead of one launch
+ * each, while the group stays within `blocks` padded 64x64-tile blocks (each
+ * member's tiles rounded up to 8; a member takes at most half of `blocks` -- a
+ * larger launch fills the chip by itself) and `members` members (at most 4).  The
+ * higher members record no fork event of their own.  Every output tile runs
+ * the code of its stand-alone launch, so no bit of the step changes.
+ * blocks: 0 = off (every dW its own launch), -1 = one resident round of the
+ * kernel on the device (512 blocks on MI355X), < -1 = leave as it is;
+ * members: 1 = off, <= 0 = leave as it is.  A group the
+ * dispatcher cannot take (a split-K member, a member knob 0 / 5 move off the
+ * 64x64 tile, more blocks than one resident round) runs as separate launches.
+ * The schedule knobs of the tune table are fixed when the handle is created;
+ * this one may be changed between steps.  A new handle starts at
+ * (MMAD_DW_GROUP_BLOCKS_DEFAULT, 4). */
+#define MMAD_DW_GROUP_BLOCKS_DEFAULT (-1)
+int mmad_ae_set_dw_group(mmad_ae* h, int blocks, int members);
+/* The grouping rule itself (pure: it reads its arguments and knob 5 only).
+ * Layers l_hi - 1 down to l_lo of an n_layers model with padded dW shapes
+ * Np[l] x Kp[l], contracting over rows[l] padded rows: group_of[l] receives the
+ * index of the layer's group in launch order, or -1 for a launch of its own.
+ * Returns the number of groups. */
+int mmad_dw_group_plan(int n_layers, const int* Np, const int* Kp, const int* rows, int l_lo, int l_hi,
+                       int budget, int members, int* group_of);
 
 /* the bf16 shadow the next kernels will read (changes after each fused step
  * when a pair is set) */
