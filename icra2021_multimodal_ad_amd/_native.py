@@ -124,7 +124,19 @@ SIGNATURES = {
     "mmad_minmax_norm_ws_bytes": (ctypes.c_size_t, [_I64, _I]),
     "mmad_minmax_norm": (_I, [_I64, _I, _P, _I, _I, _P, _P, ctypes.c_size_t, _P]),
     "mmad_nap_fit": (_I, [_I64, _I, _P, _I64, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "mmad_rank_metrics_ws_bytes": (ctypes.c_size_t, [_I64]),
+    "mmad_nap_fit_state_bytes": (_I64, [_I]),
+    "mmad_nap_fit_state_layout": (_I, [_I, ctypes.POINTER(_I64)]),
+    "mmad_nap_fit_begin": (_I, [_I, _P, _I64, _P]),
+    "mmad_nap_fit_accumulate_sums": (_I, [_I, _I, _P, _I64, _P, _I64, _P]),
+    "mmad_nap_fit_finish_mean": (_I, [_I, _I64, _P, _I64, _P, _P]),
+    "mmad_nap_fit_accumulate_gram": (_I, [_I, _I, _P, _I64, _P, _P, _I64, _P]),
+    "mmad_nap_fit_solve": (_I, [_I, _I64, _P, _I64, _P, _P]),
+    "mmad_nap_fit_accumulate_rot": (_I, [_I, _I64, _I, _P, _I64, _P, _P, _I64, _P]),
+    "mmad_nap_fit_finish": (_I, [_I, _I64, _P, _I64, _P, _P, _P]),
+    "mmad_ae_nap_fit_workspace_bytes": (_I64, [_P, _I, _I, _I]),
+    "mmad_ae_nap_fit_stream": (_I, [_P, _I, _I, _P, _I, _I64, _I, _P, _P, _P, _P, _P, _I64, _P, _I64,
+                                    _P]),
+    "mmad_rank_metrics_ws_bytes":(ctypes.c_size_t, [_I64]),
     "mmad_rank_metrics": (_I, [_I64, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "mmad_threshold_metrics_ws_bytes": (ctypes.c_size_t, [_I64]),
     "mmad_threshold_metrics": (_I, [_I64, _P, _I64, _P, _P, ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),

@@ -1794,8 +1794,16 @@ int mmad_ae_forward(mmad_ae* h, const float* x, int ld_x, int B, int train_bn, f
 // nap (nullable; needs a fit and no caller diffs): the in-range score GEMMs
 // write their diffs straight into the packed NAP operand, then the NAP GEMM
 // and its column sum write nap[0..B)
+// fit (nullable, without nap; the streaming NAP fit): the diffs of its layers
+// go, as fp32, into its own packed operand and nothing else changes
+struct DiffSink {
+  int start, end, K, Kp;   // diff layers [start, end), their width and its padding
+  bool x3;                 // bf16 plane operand (the attached fit's x3 NAP GEMM)
+  void* x;                 // [Mpe][Kp]
+};
 static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq,
-                       int64_t ld_sq, float* diffs, AeWS& w, hipStream_t st, float* nap = nullptr) {
+                       int64_t ld_sq, float* diffs, AeWS& w, hipStream_t st, float* nap = nullptr,
+                       const DiffSink* fit = nullptr) {
   // x3 (score planes attached): activations travel as bf16 planes, every
   // reference of a diff stays fp32 -- pass 1 leaves an fp32 copy of each
   // encoder output (ref32), the decoder's last layer scores against the
@@ -1808,24 +1816,27 @@ static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer
   for (int e = 0; e < h->n_enc; ++e) ld_diff += h->L[e].N;
   const mmad_ae::NapFit& nf = h->nap;
   const bool nap_x3 = nap && nf.dtype == MMAD_BF16X3;
+  const bool routed = nap || fit;
+  const DiffSink sk = nap ? DiffSink{nf.start, nf.end, nf.K, nf.Kp, nap_x3, w.nap_x}
+                          : (fit ? *fit : DiffSink{});
   // route diff layer j's diffs into the operand (columns relative to the range's first)
   auto nap_route = [&](GemmEpi& ep, int j) {
-    if (!nap || j < nf.start || j >= nf.end) return;
-    const int col = diff_col(h, j) - diff_col(h, nf.start);
-    if (nap_x3) {
-      ep.dp_hi = w.nap_x;
-      ep.dp_lo = (char*)w.nap_x + (size_t)w.Mpe * nf.Kp * 2;
-      ep.lddp = nf.Kp;
+    if (!routed || j < sk.start || j >= sk.end) return;
+    const int col = diff_col(h, j) - diff_col(h, sk.start);
+    if (sk.x3) {
+      ep.dp_hi = sk.x;
+      ep.dp_lo = (char*)sk.x + (size_t)w.Mpe * sk.Kp * 2;
+      ep.lddp = sk.Kp;
       ep.dp_col = col;
     } else {
-      ep.diff = (float*)w.nap_x + col;
-      ep.lddiff = nf.Kp;
+      ep.diff = (float*)sk.x + col;
+      ep.lddiff = sk.Kp;
     }
   };
   // the operand's padding, every batch: a ragged batch's workspace is carved
   // at other offsets than the full batches', so nothing survives from them
-  if (nap)
-    RET_IF(mmad_zero_pad(nap_x3 ? 2 : 4, nap_x3 ? 2 : 1, B, nf.K, w.Mpe, nf.Kp, w.nap_x, st));
+  if (routed)
+    RET_IF(mmad_zero_pad(sk.x3 ? 2 : 4, sk.x3 ? 2 : 1, B, sk.K, w.Mpe, sk.Kp, sk.x, st));
   // pass 1: eval forward; the decoder's last layer scores d0 = x_hat - x
   for (int l = 0; l < nL; ++l) {
     const AeLayer& a = h->L[l];
@@ -2020,6 +2031,78 @@ int mmad_ae_score_nap_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, in
   MMAD_CHECK_ARG(batch >= 1 && ws && ws_bytes >= mmad_ae_workspace_bytes(h, batch, 1),
                  "ae_score_nap_stream: bad batch or workspace too small");
   return score_stream(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, use_graph, stream);
+}
+
+// ---- streaming NAP fit ------------------------------------------------------
+// the fit's part of its workspace, after the scoring workspace of `batch`
+// windows: the packed fp32 operand [Mpe][Kp] and the passes' layer sums
+struct NapFitWS {
+  int W, Kp;
+  int64_t score_bytes, x_off, sq_off, bytes;
+};
+static bool nap_fit_carve(const mmad_ae* h, int batch, int start, int end, NapFitWS& f) {
+  if (!h || batch < 1 || start < 0 || end <= start || end > h->n_enc + 1) return false;
+  f.W = diff_col(h, end) - diff_col(h, start);
+  f.Kp = mmad_roundup(f.W, MMAD_PAD);
+  const int64_t Mp = mmad_roundup(batch, MMAD_PAD);
+  f.score_bytes = mmad_ae_workspace_bytes(h, batch, 1);
+  f.x_off = (f.score_bytes + 255) / 256 * 256;
+  f.sq_off = f.x_off + Mp * f.Kp * 4;
+  f.bytes = f.sq_off + (int64_t)(h->n_enc + 1) * Mp * 4;
+  return true;
+}
+
+int64_t mmad_ae_nap_fit_workspace_bytes(const mmad_ae* h, int batch, int start, int end) {
+  NapFitWS f;
+  return nap_fit_carve(h, batch, start, end, f) ? f.bytes : -1;
+}
+
+int mmad_ae_nap_fit_stream(mmad_ae* h, int start, int end, const float* x, int ld_x, int64_t N,
+                           int batch, float* mu_r, float* v, float* mu_s, float* var,
+                           void* fit_state, int64_t fit_bytes, void* ws, int64_t ws_bytes,
+                           void* stream) {
+  MMAD_CHECK_ARG(h && h->params && h->running, "ae_nap_fit_stream: unbound handle");
+  MMAD_CHECK_ARG(start >= 0 && end > start && end <= h->n_enc + 1,
+                 "ae_nap_fit_stream: bad layer range [%d, %d) of %d diff layers", start, end, h->n_enc + 1);
+  MMAD_CHECK_ARG(N >= 2, "ae_nap_fit_stream: a fit needs N >= 2 windows (N=%lld)", (long long)N);
+  MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && batch >= 1, "ae_nap_fit_stream: bad input or batch");
+  MMAD_CHECK_ARG(mu_r && v && mu_s && var, "ae_nap_fit_stream: null output");
+  NapFitWS f;
+  nap_fit_carve(h, batch, start, end, f);
+  MMAD_CHECK_ARG(ws && ws_bytes >= f.bytes, "ae_nap_fit_stream: workspace too small (%lld < %lld bytes)",
+                 (long long)ws_bytes, (long long)f.bytes);
+  MMAD_CHECK_ARG(((uintptr_t)ws) % 256 == 0, "ae_nap_fit_stream: workspace must be 256-byte aligned");
+  const int64_t need = mmad_nap_fit_state_bytes(f.W);
+  MMAD_CHECK_ARG(fit_state && need > 0 && fit_bytes >= need && ((uintptr_t)fit_state) % 256 == 0,
+                 "ae_nap_fit_stream: fit state too small or unaligned (%lld < %lld bytes)",
+                 (long long)fit_bytes, (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  float* op = (float*)((char*)ws + f.x_off);
+  float* sq = (float*)((char*)ws + f.sq_off);
+  const DiffSink sink{start, end, f.W, f.Kp, false, op};
+  RET_IF(refresh_planes(h, st));
+  RET_IF(mmad_nap_fit_begin(f.W, fit_state, fit_bytes, stream));
+  for (int pass = 0; pass < 3; ++pass) {
+    for (int64_t s0 = 0; s0 < N; s0 += batch) {
+      const int B = (int)std::min<int64_t>(batch, N - s0);
+      AeWS w;
+      RET_IF(prepare_ws(h, B, 1, ws, f.score_bytes, w, st));
+      RET_IF(score_batch(h, x + s0 * ld_x, ld_x, B, sq, w.Mpe, nullptr, w, st, nullptr, &sink));
+      if (pass == 0)
+        RET_IF(mmad_nap_fit_accumulate_sums(f.W, B, op, f.Kp, fit_state, fit_bytes, stream));
+      else if (pass == 1)
+        RET_IF(mmad_nap_fit_accumulate_gram(f.W, B, op, f.Kp, mu_r, fit_state, fit_bytes, stream));
+      else
+        RET_IF(mmad_nap_fit_accumulate_rot(f.W, N, B, op, f.Kp, mu_r, fit_state, fit_bytes, stream));
+    }
+    if (pass == 0)
+      RET_IF(mmad_nap_fit_finish_mean(f.W, N, fit_state, fit_bytes, mu_r, stream));
+    else if (pass == 1)
+      RET_IF(mmad_nap_fit_solve(f.W, N, fit_state, fit_bytes, v, stream));
+    else
+      RET_IF(mmad_nap_fit_finish(f.W, N, fit_state, fit_bytes, mu_s, var, stream));
+  }
+  return MMAD_OK;
 }
 
 int mmad_ae_status(mmad_ae* h, void* ws, int64_t ws_bytes, void* stream) {

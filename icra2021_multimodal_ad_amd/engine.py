@@ -482,6 +482,44 @@ class NativeAE:
              ws, nb, 1 if graph else 0, stream_ptr())
         return out
 
+    def nap_fit_stream(self, x, batch, start=0, end=None, state=None):
+        """The NAP fit of the diff layers [start, end) over the windows x
+        [N, D] (fp32, on this device), accumulated batch by batch from the
+        scoring pass (mmad_ae_nap_fit_stream): the train diffs are never
+        materialised.  Returns ({'mu_r', 'v', 'mu_s', 'var'}, the fit state
+        buffer: its column sums and Gram sit at mmad_nap_fit_state_layout's
+        offsets from its first 256-byte aligned address)."""
+        self._require(x)
+        x = self._as_input(x, self.enc_widths[0])
+        widths = self.diff_widths()
+        end = len(widths) if end is None else int(end)
+        start = int(start)
+        if not 0 <= start < end <= len(widths):
+            raise ValueError(f"nap_fit_stream: bad layer range [{start}, {end}) of {len(widths)} diff layers")
+        N = x.shape[0]
+        if N < 2:
+            raise ValueError("NAP fit needs N >= 2 windows, got %d" % N)
+        W = sum(widths[start:end])
+        R = min(N, W)
+        B = min(int(batch), N)
+        self.sync_shadow()
+        need = int(self._lib.mmad_ae_nap_fit_workspace_bytes(self._h, B, start, end))
+        if need < 0:
+            raise _native.NativeError("NAP fit workspace size query failed")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.zeros(need + 256, dtype=torch.uint8, device=self.device)
+        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
+        sb = int(self._lib.mmad_nap_fit_state_bytes(W))
+        if state is None or state.numel() < sb + 256:
+            state = torch.empty(sb + 256, dtype=torch.uint8, device=self.device)
+        sp = ctypes.c_void_p((state.data_ptr() + 255) // 256 * 256)
+        out = {"mu_r": torch.empty(W, device=self.device), "v": torch.empty((W, R), device=self.device),
+               "mu_s": torch.empty(R, device=self.device), "var": torch.empty(R, device=self.device)}
+        self.gen += 1
+        call("mmad_ae_nap_fit_stream", self._h, start, end, ptr(x), x.stride(0), N, B, ptr(out["mu_r"]),
+             ptr(out["v"]), ptr(out["mu_s"]), ptr(out["var"]), sp, sb, ws, need, stream_ptr())
+        return out, state
+
     def diff_widths(self):
         return [self.enc_widths[0]] + self.enc_widths[1:]
 

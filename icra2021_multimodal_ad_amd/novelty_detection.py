@@ -14,7 +14,9 @@ AUROC / AUPR / F1 / precision / recall.  The scores are produced on the
 device: BASE and SAP from the fused scoring pass (mmad_ae_score_stream:
 per-window squared-diff sums, the diffs never materialised), NAP from the
 device diffs (mmad_ae_score) through the native NAP run; the metrics by the
-native rank/threshold kernels (metric.py).  Train diffs are scored in batches
+native rank/threshold kernels (metric.py).  ``config.nap_fit_stream``: the
+NAP fit is accumulated from the scoring pass over the train windows instead
+(mmad_ae_nap_fit_stream; the train diffs are never materialised).  Train diffs are scored in batches
 of ``config.batch_size`` and valid/test in 698 (:36-38, get_diffs' default).
 
 Data parallel (model.dist set by dist.attach_data_parallel):
@@ -100,6 +102,13 @@ class NoveltyDetecter:
         start = getattr(cfg, "start_layer_index", 0)
         end = cfg.n_layers + 1 - getattr(cfg, "end_layer_index", -1)   # novelty_detection.py:57
         dp = model.dist if getattr(model, "dist", None) is not None and model.dist.world > 1 else None
+        fit_stream = bool(getattr(cfg, "nap_fit_stream", False))
+        if fit_stream and getattr(cfg, "train_diffs", None):
+            raise ValueError("config.nap_fit_stream never materialises the train diffs that "
+                             "config.train_diffs would save")
+        if fit_stream and dp is not None:
+            raise ValueError("config.nap_fit_stream is single-process: a data-parallel fit would "
+                             "all-reduce its sums, which is not implemented")
 
         def rows(fn, x):
             # per-window rows of fn(x): this rank's shard, all-gathered (DP)
@@ -119,12 +128,18 @@ class NoveltyDetecter:
             nap_sel = nap.sel
             sel = slice(int(cuts[nap_sel.start]), int(cuts[min(nap_sel.stop, n)]))
             nm = _nap_model(model, cfg)
-            nap_train = rows(lambda v: _device_diffs(nm, v, cfg.batch_size)[:, sel].contiguous(), train_x)
-            path = getattr(cfg, "train_diffs", None)
-            if path and (dp is None or torch.distributed.get_rank(dp.group) == 0):
-                torch.save(nap_train.cpu(), path)           # utils/metric.py:205
-            nap = NapScorer.standalone(nap_train.shape[1], device=nat.device).fit(train_diffs=nap_train)
-            del nap_train
+            if fit_stream:
+                # opt-in: the fit accumulated from the scoring pass over the train
+                # windows, batch by batch (the train diffs are never materialised)
+                nap = NapScorer.standalone(sel.stop - sel.start, device=nat.device).fit_stream(
+                    nm, train_x, cfg.batch_size, layers=(nap_sel.start, min(nap_sel.stop, n)))
+            else:
+                nap_train = rows(lambda v: _device_diffs(nm, v, cfg.batch_size)[:, sel].contiguous(), train_x)
+                path = getattr(cfg, "train_diffs", None)
+                if path and (dp is None or torch.distributed.get_rank(dp.group) == 0):
+                    torch.save(nap_train.cpu(), path)           # utils/metric.py:205
+                nap = NapScorer.standalone(nap_train.shape[1], device=nat.device).fit(train_diffs=nap_train)
+                del nap_train
             if getattr(cfg, "nap_stream", False):
                 # opt-in: valid / test NAP from the fused scoring pass (the diffs
                 # stay in the workspace); config.nap_precision picks the NAP GEMM

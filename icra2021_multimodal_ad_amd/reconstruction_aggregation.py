@@ -208,6 +208,27 @@ class NapScorer:
         self._dev = (W, R, Kp, Rp, vt, bias, w)
         return self
 
+    def fit_stream(self, model, x, batch_size, layers=None):
+        """The same fit from ``model``'s scoring pass over the train windows x
+        [N, D], batch by batch (NativeAE.nap_fit_stream): the train diffs are
+        never materialised.  layers: the diff layers [start, end) this scorer
+        covers (a standalone scorer names them; default: the range it was
+        built for)."""
+        nat = model._native
+        widths = nat.diff_widths()
+        start, stop = self.sel.start, min(self.sel.stop, len(widths))
+        if layers is not None:
+            start, stop = int(layers[0]), int(layers[1])
+        if sum(widths[start:stop]) != self.c1 - self.c0:
+            raise ValueError(f"NapScorer.fit_stream: scorer width {self.c1 - self.c0} != the model's "
+                             f"layers [{start}, {stop})")
+        model.eval()
+        with torch.no_grad():
+            x = torch.as_tensor(x).to(nat.device).float().contiguous()
+            fit_state, _ = nat.nap_fit_stream(x, batch_size, start, stop)
+        nat.check_status()
+        return self.fit(fit_state=fit_state)
+
     def score(self, diffs, precision="f32"):
         """diffs: list of per-layer arrays or [N, W] (host or device) -> [N]
         NAP scores (device fp32).  precision "bf16x3": diffs and V^T as

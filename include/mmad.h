@@ -238,6 +238,46 @@ size_t mmad_nap_fit_ws_bytes(int64_t N, int W);
 int mmad_nap_fit(int64_t N, int W, const float* x, int64_t ldx, float* mu_r, float* v, float* mu_s,
                  float* var, void* ws, size_t ws_bytes, void* stream);
 
+/* Streaming NAP fit: mmad_nap_fit's fit accumulated batch by batch, so the
+ * train diffs never exist as one matrix.  A batch is a device fp32 matrix
+ * d[B][ld] with W valid columns (ld >= W; whatever lies past them is neither
+ * read nor written).  state: a caller-owned, 256-byte aligned device buffer of
+ * mmad_nap_fit_state_bytes(W) bytes (-1: bad W), whatever the batch sizes.
+ * The caller runs three passes over the same batches, N rows in all:
+ *   begin;  accumulate_sums(batch)...;  finish_mean(N) -> mu_r [W]
+ *   accumulate_gram(batch, mu_r)...;    solve(N) -> v [W][R], R = min(N, W)
+ *   accumulate_rot(batch, mu_r)...;     finish(N) -> mu_s [R], var [R]
+ * accumulate_sums: fp64 column sums, rows in order; mu_r = fp32(S / N).
+ * accumulate_gram: first centres the batch IN PLACE (d -= mu_r, fp32, rows < B
+ *   and columns < W only: padding stays what it was), then adds its Gram to
+ *   the running fp64 G on v_mfma_f64_16x16x4_f64 (exact products; only the
+ *   upper-triangular 128x128 tiles are kept).
+ * solve: mirrors G into a second matrix (G stays readable), rocSOLVER dsyevd,
+ *   eigenvectors in descending order as mmad_nap_fit; synchronises `stream`.
+ * accumulate_rot: takes the batch UNCENTRED, as the first pass saw it, and
+ *   leaves it untouched: rot = fp32(d - mu_r) v per 2048-row chunk through the
+ *   exact-fp32 GEMM, fp64 sum / sum of squares per column.
+ * finish: mu_s = fp32(mean), var = fp32(sum (rot - mean)^2 / (N - 1)).
+ * No atomics: for the same batches a repeated fit is bit-identical.
+ * mmad_nap_fit_state_layout: info int64[3] = byte offsets of the fp64 column
+ * sums [W] and of G [W][W] (row-major, upper triangle valid) in the state,
+ * and the state's size.  MMAD_EINVAL (nothing launched): N < 2, B < 1, a null
+ * pointer, ld < W, a state that is too small or unaligned. */
+int64_t mmad_nap_fit_state_bytes(int W);
+int mmad_nap_fit_state_layout(int W, int64_t* info);
+int mmad_nap_fit_begin(int W, void* state, int64_t state_bytes, void* stream);
+int mmad_nap_fit_accumulate_sums(int W, int B, const float* d, int64_t ld, void* state,
+                                 int64_t state_bytes, void* stream);
+int mmad_nap_fit_finish_mean(int W, int64_t N, void* state, int64_t state_bytes, float* mu_r,
+                             void* stream);
+int mmad_nap_fit_accumulate_gram(int W, int B, float* d, int64_t ld, const float* mu_r, void* state,
+                                 int64_t state_bytes, void* stream);
+int mmad_nap_fit_solve(int W, int64_t N, void* state, int64_t state_bytes, float* v, void* stream);
+int mmad_nap_fit_accumulate_rot(int W, int64_t N, int B, const float* d, int64_t ld,
+                                const float* mu_r, void* state, int64_t state_bytes, void* stream);
+int mmad_nap_fit_finish(int W, int64_t N, void* state, int64_t state_bytes, float* mu_s, float* var,
+                        void* stream);
+
 /* Backward of Linear (autograd of layers/fc_layer.py:38):
  * dx[Mp][Kp] = dz[Mp][Np] . w[Np][Kp]; colsum (nullable, [Mp/32][2][Kp]
  * slot 0) = per-chunk column sums of dx (bias grad of a no-BN producer). */
@@ -651,6 +691,29 @@ int mmad_ae_score_nap_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, in
                              float* layer_sq, int64_t ld_sq, float* nap, void* ws, int64_t ws_bytes,
                              int use_graph, void* stream);
 int mmad_ae_nap_operand(const mmad_ae* h, int B, int64_t* info);
+
+/* Streaming NAP fit from the scoring pass: the fit of the concatenated diffs
+ * of the diff layers [start, end) over the N windows x [N][ld_x], the diffs
+ * never materialised.  Three eager passes over x in batches of `batch`
+ * windows on the handle's score path (whatever its score dtype); in each, the
+ * in-range score GEMMs write a batch's diffs as fp32 into a packed operand
+ * [Mp][Kp] (as the streamed NAP score's fp32 operand) and the mmad_nap_fit_*
+ * step of that pass reads it: sums; centre + Gram, then solve; rotated
+ * moments.  At most one batch of diffs exists at any time.  Outputs as
+ * mmad_nap_fit (W = the range's width, R = min(N, W)); fit_state: an
+ * mmad_nap_fit_state_bytes(W) buffer, left holding the sums and G.  ws:
+ * mmad_ae_nap_fit_workspace_bytes(h, batch, start, end) bytes (-1: bad
+ * arguments) = the scoring workspace of `batch` windows, its offsets
+ * unchanged, followed by the operand and the pass's layer sums.  No fit needs
+ * to be attached and an attached one, the graph cache and every other entry
+ * point's results are untouched.  Synchronises `stream` (the solve).
+ * MMAD_EINVAL (nothing launched): N < 2, a bad layer range, a null output, a
+ * workspace or fit state that is too small. */
+int64_t mmad_ae_nap_fit_workspace_bytes(const mmad_ae* h, int batch, int start, int end);
+int mmad_ae_nap_fit_stream(mmad_ae* h, int start, int end, const float* x, int ld_x, int64_t N,
+                           int batch, float* mu_r, float* v, float* mu_s, float* var,
+                           void* fit_state, int64_t fit_bytes, void* ws, int64_t ws_bytes,
+                           void* stream);
 
 /* Split-K health of the executor workspace `ws` (as mmad_gemm_status): a
  * no-op returning MMAD_OK unless split-K is enabled (tuning knob 4 > 1);
