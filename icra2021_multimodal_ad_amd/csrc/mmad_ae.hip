@@ -1064,383 +1064,437 @@ static BiasSrc bias_src(const mmad_ae* h, const AeWS& w, int l, bool from_mse) {
 
 using AdamHyper = MmadAdamConsts;   // w1 = float(1 - beta1), w2 = float(1 - beta2), ...
 
-// backward through every layer.  from_mse: the last layer's dz and bias
-// partials come from the MSE-fused forward epilogue; otherwise the caller has
-// packed dL/dx_hat into the last layer's dy buffer.  adam != null: each
-// layer's Adam update runs on the side stream right after its dW GEMM.
 static int finish_reductions(mmad_ae* h, AeWS& w, bool biases, bool from_mse, float beta_kl,
                              float* loss_out, hipStream_t st);
 
-// dp_loss (data-parallel fused step): the loss output; the bias / gamma / beta
-// bucket and the loss are reduced and exchanged as soon as the backward chain
-// has produced the last bias partials, ahead of layer 0's weight bucket
-// side_after_mse: the side stream already waits for the MSE launch (the fused
-// step's loss reduction), so the top layer's dW needs no fork of its own
-static int run_backward(mmad_ae* h, AeWS& w, bool from_mse, float beta_kl, const AdamHyper* adam,
-                        hipStream_t st, float* dp_loss = nullptr, bool side_after_mse = false) {
-  const int dt = h->dtype;
-  const int nL = (int)h->L.size();
-  hipStream_t side = h->side;
-  std::vector<PendingDW> pending;   // side-stream dW GEMMs waiting for a recorded event
-  // ev_fork[l] completed by the launch that produced dz_l (knob 34)
-  std::vector<char> fork_done(nL, 0);
-  const bool fork_kev = h->fork_on_kernel && !h->capturing;
-  // does layer l's side-stream dW (ping) get a fork event of its own (knob 35)?
+// One backward pass: the main-stream bwd-data chain (bwd_data_step), written
+// once, and one of three dW policies hooked in before and after each step --
+// plain (no Adam), data-parallel (Adam after the bucket's exchange) and fused
+// (single GPU, Adam in the dW epilogue).  This is the state they share.
+struct BwdRun {
+  mmad_ae* h;
+  AeWS& w;
+  hipStream_t st, side;
+  // non-null: the step's Adam update runs in the dW epilogues (fused) or
+  // after each bucket's exchange (data parallel, h->comm)
+  const AdamHyper* adam;
+  // the last layer's dz and bias partials come from the MSE-fused forward
+  // epilogue; otherwise the caller has packed dL/dx_hat into its dy buffer
+  bool from_mse;
+  // the side stream already waits for the MSE launch (the fused step's loss
+  // reduction), so the top layer's dW needs no fork of its own
+  bool side_after_mse;
+  float beta_kl;
+  float* dp_loss;                   // data parallel: the loss output (dp_small_bucket)
+  int nL;
+  bool fork_kev;                    // fork events ride the producing launch (knob 34)
+  std::vector<PendingDW> pending;   // dW GEMMs waiting for a recorded event
+  std::vector<char> fork_done;      // ev_fork[l] completed by the launch that produced dz_l
   // grouped dW launches (single-GPU ping-pong step only): grp[l] = the group
   // layer l's dW + Adam GEMM is issued with, -1 = a launch of its own
-  std::vector<int> grp(nL, -1);
-  if (adam && !h->comm && w.ping && !h->capturing && !h->side_hold && h->dw_group_blocks != 0) {
-    std::vector<int> np(nL), kp(nL), rows(nL);
-    for (int l = 0; l < nL; ++l) {
-      np[l] = h->L[l].Np;
-      kp[l] = h->L[l].Kp;
-      rows[l] = prows_of(w, h->L[l]);
-    }
-    const int budget = h->dw_group_blocks < 0 ? mmad_gemm_group_capacity(dt) : h->dw_group_blocks;
-    mmad_dw_group_plan(nL, np.data(), kp.data(), rows.data(), w.dw_main, nL - h->dw_late, budget,
-                       h->dw_group_members, grp.data());
+  std::vector<int> grp;
+  std::vector<DpBucket> plan;       // data parallel: the exchange buckets (dp_plan)
+  size_t next_bucket = 0;
+
+  bool dp() const { return adam && h->comm; }
+  bool fused() const { return adam && !h->comm; }
+  // the exchange bucket still open (data parallel), and whether layer l closes it
+  const DpBucket* open_bucket() const { return next_bucket < plan.size() ? &plan[next_bucket] : nullptr; }
+  const DpBucket* closes_bucket(int l) const {
+    return open_bucket() && open_bucket()->l_lo == l ? open_bucket() : nullptr;
   }
-  // issue the deferred side-stream dW GEMMs, then `cur`: members of one group
-  // (adjacent in issue order) as one launch, every other -- and a group the
-  // dispatcher refuses -- as its own
-  auto issue_side = [&](const PendingDW& cur) -> int {
-    pending.push_back(cur);
-    for (size_t i = 0; i < pending.size();) {
-      const int gid = grp[pending[i].layer];
-      size_t j = i + 1;
-      while (gid >= 0 && j < pending.size() && grp[pending[j].layer] == gid) ++j;
-      int rc = MMAD_GEMM_GROUP_REFUSED;
-      if (j - i >= 2) rc = ae_gemm_group(h, w, dt, &pending[i], (int)(j - i), side);
-      if (rc == MMAD_GEMM_GROUP_REFUSED) {
-        for (size_t m = i; m < j; ++m) {
-          const PendingDW& q = pending[m];
-          RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, q.dz, q.lda, q.in, q.ldb, q.M, q.N, q.K, q.ep,
-                         side, nullptr, PROBE_DW + q.layer));
-        }
-      } else if (rc != MMAD_OK) {
-        return rc;
-      }
-      i = j;
-    }
-    pending.clear();
-    return MMAD_OK;
-  };
-  auto fork_ev = [&](int l) {
+  // ping-pong shadows (bf16): the fused Adam of dW_l writes the other shadow,
+  // so dW_l may start as soon as dz_l is complete
+  bool ping(int l) const { return fused() && w.ping && l >= w.dw_main; }
+  bool late(int l) const { return ping(l) && l >= nL - h->dw_late; }
+  // does layer l's side-stream dW (ping) get a fork event of its own (knob 35)?
+  bool fork_ev(int l) const {
     // a group forks once, at its lowest member
     if (grp[l] >= 0) return l == 0 || grp[l - 1] != grp[l];
     const int P = h->fork_pair_below;
     if (P <= 0 || l > P || l == w.dw_main) return true;
     return (P - l) % 2 == 1;
-  };
-  auto forks_at_dz = [&](int l) {   // does layer l's side-stream dW fork behind dz_l (ping, not late)?
-    return adam && !h->comm && w.ping && l >= w.dw_main && l < nL - h->dw_late && fork_ev(l);
-  };
-  std::vector<DpBucket> plan;       // data parallel: the exchange buckets (dp_plan)
-  int next_bucket = 0;
-  if (adam && h->comm) dp_plan(h, plan);
-  // layer l's Adam terms for a dW epilogue: the weight tile's (ad_*, unless
-  // weights_too is false) and the small segment [bias | gamma | beta]'s
-  auto fill_adam = [&](GemmEpi& e, int l, bool weights_too) {
-    const AeLayer& a = h->L[l];
-    const BiasSrc bs = bias_src(h, w, l, from_mse);
-    if (weights_too) {
-      e.ad_p = h->params + a.w_off;
-      e.ad_m = h->m + a.w_off;
-      e.ad_v = h->v + a.w_off;
-      e.ad_shadow = adam_shadow(h, a, w.ping);
-      // the gradient is consumed by the fused Adam in registers; materialise
-      // it only when asked (h->keep_grads)
-      e.dw_nostore = h->keep_grads ? 0 : 1;
-    }
-    e.ad_w1 = adam->w1;
-    e.ad_w2 = adam->w2;
-    e.ad_eps = adam->eps;
-    e.ad_step = adam->step_size;
-    e.ad_bc2 = adam->bc2_sqrt;
+  }
+  // does layer l's side-stream dW fork behind dz_l (ping, not late)?
+  bool forks_at_dz(int l) const { return ping(l) && !late(l) && fork_ev(l); }
+  // the top layer's dz is the MSE output, which the side stream has waited
+  // for already (the loss reduction): no fork
+  bool fork_none(int l) const {
+    return ping(l) && !late(l) && l == nL - 1 && from_mse && side_after_mse && fork_kev;
+  }
+  // does someone wait for ev_data[l] (bwd-data of l done)?  The DP exchange
+  // of the bucket l closes, and the fused step's side-stream dW GEMMs without
+  // ping-pong shadows (every ev_every-th layer; the lowest side layer always
+  // records, flushing the deferred ones)
+  bool needs_data_ev(int l) const {
+    if (dp()) return closes_bucket(l) != nullptr;
+    if (!fused() || ping(l) || l < w.dw_main) return false;
+    return h->ev_every <= 1 || l == w.dw_main || (l - w.dw_main) % h->ev_every == 0;
+  }
+};
+
+// `ev` recorded on `from`, waited for on `to`
+static int hand_off(hipEvent_t ev, hipStream_t from, hipStream_t to) {
+  MMAD_HIP_CHECK(hipEventRecord(ev, from));
+  MMAD_HIP_CHECK(hipStreamWaitEvent(to, ev, 0));
+  return MMAD_OK;
+}
+
+static const void* dz_of(const BwdRun& r, int l) {
+  const AeLayer& a = r.h->L[l];
+  const LayerWS& s = r.w.l[l];
+  return (l == r.nL - 1) ? (r.from_mse ? s.out : s.dy) : (a.bn ? s.dz : s.dy);
+}
+
+// Layer l's dW problem.  Only once the bwd-data of layer l+1 has been emitted:
+// bias_src(l) reads the bwd_fused flag that step sets.
+static PendingDW make_dw(const BwdRun& r, int l) {
+  const mmad_ae* h = r.h;
+  const AeWS& w = r.w;
+  const AeLayer& a = h->L[l];
+  const float *isc, *ish;
+  const void* in = input_of(h, w, l, true, &isc, &ish);
+  GemmEpi e{};
+  e.M = a.Np;
+  e.N = a.Kp;
+  e.out = h->grads + a.w_off;
+  e.ldo = a.Kp;
+  if (isc) {
+    // dW against the raw producer activation, fixed up in the epilogue
+    e.b_scale = isc;
+    e.b_shift = ish;
+  }
+  if (r.fused()) {
+    // this layer's Adam update in the epilogue: the weight tile's terms ...
+    e.ad_p = h->params + a.w_off;
+    e.ad_m = h->m + a.w_off;
+    e.ad_v = h->v + a.w_off;
+    e.ad_shadow = adam_shadow(h, a, w.ping);
+    // the gradient is consumed by the fused Adam in registers; materialise
+    // it only when asked (h->keep_grads)
+    e.dw_nostore = h->keep_grads ? 0 : 1;
+    e.ad_w1 = r.adam->w1;
+    e.ad_w2 = r.adam->w2;
+    e.ad_eps = r.adam->eps;
+    e.ad_step = r.adam->step_size;
+    e.ad_bc2 = r.adam->bc2_sqrt;
     e.dyn = w.dyn;
+    // ... and the small segment [bias | gamma | beta]'s
     e.sm_p = h->params + a.b_off;
     e.sm_g = h->grads + a.b_off;
     e.sm_m = h->m + a.b_off;
     e.sm_v = h->v + a.b_off;
     e.sm_n = a.bn ? 3 * a.Np : a.Np;
+    e.sm_bN = a.N;
+    e.sm_bNp = a.Np;
+  }
+  if (isc || r.fused()) {
+    const BiasSrc bs = bias_src(h, w, l, r.from_mse);
     e.gb_src = bs.src;
     e.gb_parts = bs.nparts;
     e.gb_stride = bs.stride;
-    e.sm_bN = a.N;
-    e.sm_bNp = a.Np;
-  };
-  for (int l = nL - 1; l >= 0; --l) {
-    const AeLayer& a = h->L[l];
-    LayerWS& s = w.l[l];
-    const int Mp = prows_of(w, a);
-    const void* dz = (l == nL - 1) ? (from_mse ? s.out : s.dy) : (a.bn ? s.dz : s.dy);
-    const float *isc, *ish;
-    const void* in = input_of(h, w, l, true, &isc, &ish);
-    GemmEpi dwe{};
-    dwe.M = a.Np;
-    dwe.N = a.Kp;
-    dwe.out = h->grads + a.w_off;
-    dwe.ldo = a.Kp;
-    if (isc) {
-      // dW against the raw producer activation, fixed up in the epilogue
-      const BiasSrc gs = bias_src(h, w, l, from_mse);
-      dwe.b_scale = isc;
-      dwe.b_shift = ish;
-      dwe.gb_src = gs.src;
-      dwe.gb_parts = gs.nparts;
-      dwe.gb_stride = gs.stride;
-    }
-    const bool dp = adam && h->comm;
-    // the exchange bucket this layer closes (data parallel), if any
-    const DpBucket* bk = nullptr;
-    const DpBucket* cur = dp && next_bucket < (int)plan.size() ? &plan[next_bucket] : nullptr;
-    if (cur && cur->l_lo == l) bk = &plan[next_bucket++];
-    // ping-pong shadows (bf16): the fused Adam of dW_l writes the other
-    // shadow, so dW_l may start as soon as dz_l is complete
-    const bool ping = adam && !dp && w.ping && l >= w.dw_main;
-    const bool late = ping && l >= nL - h->dw_late;
-    // the top layer's dz is the MSE output, which the side stream has waited
-    // for already (the loss reduction): no fork
-    const bool fork_none = ping && !late && l == nL - 1 && from_mse && side_after_mse && fork_kev;
-    if (ping && !late && !fork_none && !fork_done[l] && fork_ev(l)) {
-      MMAD_HIP_CHECK(hipEventRecord(h->ev_fork[l], st));
-    }
-    // does the main stream record ev_data[l] (bwd-data of l done)?  Needed by
-    // the DP exchange and by side-stream dW GEMMs (every ev_every-th layer;
-    // the lowest side layer always records, flushing the deferred ones)
-    const bool side_dw = adam && !dp && !ping && l >= w.dw_main;
-    const bool rec = bk || (side_dw && (h->ev_every <= 1 || l == w.dw_main ||
-                                        (l - w.dw_main) % h->ev_every == 0));
-    bool ev_attached = false;   // ev_data[l] completed by the bwd-data launch (ev_on_kernel)
-    if (dp) {
-      // data parallel: below dp_fork_rows rows (host-bound steps, every event
-      // call counts) the dW GEMMs of a bucket's layers are issued together
-      // once the layer that closes it has its dz (one fork per bucket), then
-      // the bucket's event
-      // from dp_fork_rows rows the step is GPU-bound: a side-stream bucket's
-      // dW GEMMs then start at their own dz (one fork each) instead of
-      // queueing until the bucket's lowest layer
-      const bool each = h->dp_fork_rows > 0 && Mp >= h->dp_fork_rows && cur &&
-                        !(cur->l_hi < w.dw_main);
-      if (each) {
-        MMAD_HIP_CHECK(hipEventRecord(h->ev_fork[l], st));
-        MMAD_HIP_CHECK(hipStreamWaitEvent(side, h->ev_fork[l], 0));
-        // (a bucket whose upper layers were below the row threshold: their
-        // dW GEMMs go first, so the bucket's event below covers them too)
-        for (const PendingDW& q : pending)
-          RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, q.dz, q.lda, q.in, q.ldb, q.M, q.N, q.K, q.ep,
-                         side, nullptr, PROBE_DW + q.layer));
-        pending.clear();
-        RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, dz, a.Np, in, a.Kp, a.Np, a.Kp, Mp, dwe, side,
-                       nullptr, PROBE_DW + l));
-        if (bk) MMAD_HIP_CHECK(hipEventRecord(h->ev_dw[l], side));
-      } else {
-        pending.push_back(PendingDW{dz, in, a.Np, a.Kp, a.Np, a.Kp, Mp, dwe, l});
-      }
-      if (bk && !each) {
-        // a bucket made only of the last dw_main layers of the chain runs its
-        // dW GEMMs on the main stream, idle by then, instead of behind the
-        // side stream's backlog (the exchange tail waits for them)
-        const bool on_main = bk->l_hi < w.dw_main;
-        hipStream_t ds = on_main ? st : side;
-        if (!on_main) {
-          MMAD_HIP_CHECK(hipEventRecord(h->ev_fork[l], st));
-          MMAD_HIP_CHECK(hipStreamWaitEvent(side, h->ev_fork[l], 0));
-        }
-        for (const PendingDW& q : pending)
-          RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, q.dz, q.lda, q.in, q.ldb, q.M, q.N, q.K, q.ep,
-                         ds, nullptr, PROBE_DW + q.layer));
-        pending.clear();
-        MMAD_HIP_CHECK(hipEventRecord(h->ev_dw[l], ds));
-      }
-    } else if (!adam) {
-      // fork: dz_l is complete on the main stream; dW_l overlaps the chain below
-      MMAD_HIP_CHECK(hipEventRecord(h->ev_fork[l], st));
-      MMAD_HIP_CHECK(hipStreamWaitEvent(side, h->ev_fork[l], 0));
-      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, dz, a.Np, in, a.Kp, a.Np, a.Kp, Mp, dwe, side,
-                     nullptr, PROBE_DW + l));
-      if (h->dw_events) MMAD_HIP_CHECK(hipEventRecord(h->ev_xdw[l], side));
-    }
-    if (l > 0) {
-      const AeLayer& p = h->L[l - 1];
-      LayerWS& ps = w.l[l - 1];
-      const int M = rows_of(w, a);
-      const int Mpp = prows_of(w, p);
-      GemmEpi ep{};
-      ep.M = M;
-      ep.N = a.K;
-      ep.ldo = a.Kp;
-      ep.ldpart = a.Kp;
-      // dz_{l-1} is produced below: its side-stream dW fork rides on that launch
-      const bool attach = fork_kev && forks_at_dz(l - 1);
-      if (h->vib && l == h->n_enc) {
-        ep.out = w.dzin;
-        RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_DATA, dz, a.Np, weights(h, a), a.Kp, Mp, a.Kp,
-                                  a.Np, ep, st));
-        RET_IF(mmad_vib_reparam_bwd(dt, w.B, h->btl, w.k, ps.out, p.Np, w.eps, w.dzin, a.Kp,
-                                    beta_kl, ps.dy, p.Np, ps.dbpart, st));
-      } else if (p.bn) {
-        ep.out = ps.dy;
-        ep.bn_a = ps.out;
-        ep.bn_mean = ps.mean;
-        ep.bn_rstd = ps.rstd;
-        ep.bn_part = ps.bnpart;
-        ps.bwd_fused = w.bn_mode_bwd == 2 && mmad_gemm_bn_fusable(dt, GEMM_EPI_BWD_DATA, Mp, a.Kp);
-        if (ps.bwd_fused) {
-          // BN + activation backward of layer l-1 inside this GEMM: dz directly
-          ep.out = nullptr;
-          ep.bn_sync = ps.sync_b;
-          ep.bn_err = w.bn_err;
-          ep.bn_gamma = h->params + p.g_off;
-          ep.bn_dz = ps.dz;
-          ep.bn_dgamma = h->grads + p.g_off;
-          ep.bn_dbeta = h->grads + p.be_off;
-          ep.bn_dbpart = ps.dbpart;
-          ep.bn_act = p.act;
-          ep.slope = h->slope;
-        }
-        if (rec && h->ev_on_kernel && !h->capturing) {
-          ep.done_ev = h->ev_data[l];
-          ev_attached = true;
-        }
-        if (attach && ps.bwd_fused && !ep.done_ev) {
-          ep.done_ev = h->ev_fork[l - 1];
-          fork_done[l - 1] = 1;
-        }
-        RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_DATA, dz, a.Np, weights(h, a), a.Kp, Mp, a.Kp,
-                                  a.Np, ep, st));
-        if (rec && !ev_attached) MMAD_HIP_CHECK(hipEventRecord(h->ev_data[l], st));
-        if (!ps.bwd_fused) {
-          RET_IF(mmad_bn_act_bwd_apply_ev(dt, p.act, h->slope, rows_of(w, p), p.N, Mpp, p.Np, ps.dy,
-                                          ps.out, ps.mean, ps.rstd, h->params + p.g_off, ps.bnpart,
-                                          Mpp / 64, ps.dz, h->grads + p.g_off, h->grads + p.be_off,
-                                          ps.dbpart, st, attach ? h->ev_fork[l - 1] : nullptr));
-          if (attach) fork_done[l - 1] = 1;
-        }
-      } else {
-        ep.out = ps.dy;
-        ep.part = ps.stats;
-        if (rec && h->ev_on_kernel && !h->capturing) {
-          ep.done_ev = h->ev_data[l];
-          ev_attached = true;
-        }
-        if (attach && !ep.done_ev) {
-          ep.done_ev = h->ev_fork[l - 1];
-          fork_done[l - 1] = 1;
-        }
-        RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_DATA, dz, a.Np, weights(h, a), a.Kp, Mp, a.Kp,
-                                  a.Np, ep, st));
-      }
-    }
-    // torch exchange: W_l is read for the last time by the bwd-data of l
-    if (!adam && h->dw_events && l > 0) MMAD_HIP_CHECK(hipEventRecord(h->ev_xdata[l], st));
-    if (dp && dp_loss && l == (nL > h->dp_small_at ? h->dp_small_at : 0)) {
-      // the last bwd-data (l = 1, just enqueued) has produced every bias
-      // partial and the loss partials are the forward's: reduce them on the
-      // main stream now and queue the small bucket's exchange + Adam on the
-      // comm stream ahead of layer 1's and layer 0's weight buckets, so it
-      // runs while their dW GEMMs still compute instead of after them
-      RET_IF(finish_reductions(h, w, true, true, beta_kl, dp_loss, st));
-      MMAD_HIP_CHECK(hipEventRecord(h->ev_small, st));
-      MMAD_HIP_CHECK(hipStreamWaitEvent(h->cstream, h->ev_small, 0));
-      const int64_t ns = h->n_params - h->n_weight;
-      RET_IF(mmad_allreduce_pair(h->comm, h->grads + h->n_weight, ns, dp_loss, 1, h->cstream));
-      RET_IF(mmad_adam_w(ns, h->params + h->n_weight, h->grads + h->n_weight, h->m + h->n_weight,
-                       h->v + h->n_weight, adam->w1, adam->w2, adam->eps, adam->step_size,
-                       adam->bc2_sqrt, nullptr, 0, h->cstream));
-    }
-    if (bk) {
-      // data parallel: exchange the bucket this layer closes (layers
-      // bk->l_hi .. l, one contiguous weight range) on the comm stream as soon
-      // as its last dW GEMM is complete, then its Adam update (which rewrites
-      // the bucket's weights, so it also waits for the main stream's bwd-data
-      // of layer l, the last GEMM of the chain that reads them)
-      if ((l == 0 || !(h->L[l - 1].bn) || (h->vib && l == h->n_enc)) && !ev_attached)
-        MMAD_HIP_CHECK(hipEventRecord(h->ev_data[l], st));
-      MMAD_HIP_CHECK(hipStreamWaitEvent(h->cstream, h->ev_data[l], 0));
-      const int nr = mmad_comm_size(h->comm) > 0 ? mmad_comm_size(h->comm) : 1;
-      MMAD_HIP_CHECK(hipStreamWaitEvent(h->cstream, h->ev_dw[l], 0));
-      {
-        const int64_t n = bk->n, boff = bk->off;
-        if (h->dp_shard && n % nr == 0 && (n / nr) % 4 == 0) {
-          // ZeRO-1 form: reduce-scatter, Adam on this rank's shard, all-gather
-          // of the updated weights the next step reads (bf16 shadow / fp32 p)
-          const int64_t cnt = n / nr, off = boff + (int64_t)mmad_comm_rank(h->comm) * cnt;
-          if (h->grad_bf16) {
-            // bf16 on the wire: round the bucket, reduce-scatter, widen this rank's slice
-            char* gb = (char*)h->grad_bf16;
-            RET_IF(mmad_to_bf16(n, h->grads + boff, gb + boff * 2, h->cstream));
-            RET_IF(mmad_reduce_scatter_bucket_bf16(h->comm, gb + boff * 2, n, h->cstream));
-            RET_IF(mmad_from_bf16(cnt, gb + off * 2, h->grads + off, h->cstream));
-          } else {
-            RET_IF(mmad_reduce_scatter_bucket(h->comm, h->grads + boff, n, h->cstream));
-          }
-          void* sh = h->dtype == MMAD_BF16 ? (void*)((char*)h->shadow + off * 2) : nullptr;
-          RET_IF(mmad_adam_w(cnt, h->params + off, h->grads + off, h->m + off, h->v + off, adam->w1,
-                           adam->w2, adam->eps, adam->step_size, adam->bc2_sqrt, sh,
-                           h->dtype == MMAD_BF16 ? cnt : 0, h->cstream));
-          if (h->dtype == MMAD_BF16)
-            RET_IF(mmad_all_gather_bucket(h->comm, (char*)h->shadow + boff * 2, n, MMAD_BF16, h->cstream));
-          else
-            RET_IF(mmad_all_gather_bucket(h->comm, h->params + boff, n, MMAD_F32, h->cstream));
-          if (nr > 1) h->master_stale = true;
-        } else {
-          RET_IF(mmad_allreduce_bucket(h->comm, h->grads + boff, n, h->cstream));
-          void* sh = adam_shadow(h, a, w.ping);
-          RET_IF(mmad_adam_w(n, h->params + boff, h->grads + boff, h->m + boff, h->v + boff,
-                           adam->w1, adam->w2, adam->eps, adam->step_size, adam->bc2_sqrt,
-                           sh, h->dtype == MMAD_BF16 ? n : 0, h->cstream));
-        }
-      }
-    } else if (adam && !dp) {
-      // dW_l with this layer's Adam update fused into its epilogue.  It rewrites
-      // W_l, so it starts only once the main stream has finished reading W_l
-      // (bwd-data of l); the rest of the chain keeps overlapping it.
-      if (rec && !ev_attached && (l == 0 || !(h->L[l - 1].bn) || (h->vib && l == h->n_enc)))
-        MMAD_HIP_CHECK(hipEventRecord(h->ev_data[l], st));
-      fill_adam(dwe, l, true);
-      // the last dW GEMMs of the chain go to the main stream, which is idle
-      // by then, instead of queueing behind the side stream's backlog
-      const bool on_main = l < w.dw_main;
-      if (on_main) {
-        dwe.tile_force = mmad_tile_adam_main_for(a.Np, a.Kp, Mp) + 1;
-        RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, dz, a.Np, in, a.Kp, a.Np, a.Kp, Mp, dwe, st,
-                       nullptr, PROBE_DW + l));
-      } else if (h->side_hold) {
-        pending.push_back(PendingDW{dz, in, a.Np, a.Kp, a.Np, a.Kp, Mp, dwe, l});
-      } else if (ping && !late && !fork_ev(l)) {
-        // no fork of its own: issued with the next lower layer's dW
-        pending.push_back(PendingDW{dz, in, a.Np, a.Kp, a.Np, a.Kp, Mp, dwe, l});
-      } else if (ping) {
-        if (late) MMAD_HIP_CHECK(hipEventRecord(h->ev_fork[l], st));
-        if (!fork_none) MMAD_HIP_CHECK(hipStreamWaitEvent(side, h->ev_fork[l], 0));
-        RET_IF(issue_side(PendingDW{dz, in, a.Np, a.Kp, a.Np, a.Kp, Mp, dwe, l}));
-      } else if (!rec) {
-        pending.push_back(PendingDW{dz, in, a.Np, a.Kp, a.Np, a.Kp, Mp, dwe, l});
-      } else {
-        MMAD_HIP_CHECK(hipStreamWaitEvent(side, h->ev_data[l], 0));
-        for (const PendingDW& q : pending)
-          RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, q.dz, q.lda, q.in, q.ldb, q.M, q.N, q.K, q.ep,
-                         side, nullptr, PROBE_DW + q.layer));
-        pending.clear();
-        RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, dz, a.Np, in, a.Kp, a.Np, a.Kp, Mp, dwe, side,
-                       nullptr, PROBE_DW + l));
-      }
-    }
   }
-  if (h->side_hold && !pending.empty()) {
-    MMAD_HIP_CHECK(hipEventRecord(h->ev_hold, st));
-    MMAD_HIP_CHECK(hipStreamWaitEvent(side, h->ev_hold, 0));
-    for (const PendingDW& q : pending)
-      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_WEIGHT, q.dz, q.lda, q.in, q.ldb, q.M, q.N, q.K, q.ep, side,
-                     nullptr, PROBE_DW + q.layer));
-    pending.clear();
+  return PendingDW{dz_of(r, l), in, a.Np, a.Kp, a.Np, a.Kp, prows_of(w, a), e, l};
+}
+
+static int launch_dw(const BwdRun& r, const PendingDW& q, hipStream_t s) {
+  return ae_gemm(r.h, r.w, r.h->dtype, GEMM_EPI_BWD_WEIGHT, q.dz, q.lda, q.in, q.ldb, q.M, q.N, q.K,
+                 q.ep, s, nullptr, PROBE_DW + q.layer);
+}
+
+// issue the deferred dW GEMMs in order on `s`: members of one group (adjacent
+// in issue order) as one launch, every other -- and a group the dispatcher
+// refuses -- as its own
+static int flush(BwdRun& r, hipStream_t s) {
+  std::vector<PendingDW>& p = r.pending;
+  for (size_t i = 0; i < p.size();) {
+    const int gid = r.grp[p[i].layer];
+    size_t j = i + 1;
+    while (gid >= 0 && j < p.size() && r.grp[p[j].layer] == gid) ++j;
+    int rc = MMAD_GEMM_GROUP_REFUSED;
+    if (j - i >= 2) rc = ae_gemm_group(r.h, r.w, r.h->dtype, &p[i], (int)(j - i), s);
+    if (rc == MMAD_GEMM_GROUP_REFUSED) {
+      for (size_t m = i; m < j; ++m) RET_IF(launch_dw(r, p[m], s));
+    } else if (rc != MMAD_OK) {
+      return rc;
+    }
+    i = j;
   }
-  MMAD_CHECK_ARG(pending.empty(), "ae backward: deferred dW GEMMs left unissued");
-  // join the side stream back into the main stream
-  MMAD_HIP_CHECK(hipEventRecord(h->ev_join, side));
-  MMAD_HIP_CHECK(hipStreamWaitEvent(st, h->ev_join, 0));
+  p.clear();
   return MMAD_OK;
+}
+
+// which of its two events a chain step got completed on the main stream
+struct ChainPlaced { bool done, fork; };
+
+// The main-stream chain element: bwd-data GEMM of layer l (dz_l -> dy_{l-1})
+// plus what turns dy_{l-1} into dz_{l-1} outside a GEMM epilogue (the VIB
+// reparameterisation backward, the BN + activation backward apply).  The only
+// writer of bwd_fused.  done_ev (nullable) is to complete with the GEMM,
+// fork_below (nullable) with the launch that produces dz_{l-1}; a launch
+// completes one event, and done_ev goes first.  done_ev that cannot ride the
+// GEMM is recorded behind it when a BN apply follows, and is otherwise left
+// to the caller; fork_below is only ever attached.
+static int bwd_data_step(BwdRun& r, int l, hipEvent_t done_ev, hipEvent_t fork_below, ChainPlaced* placed) {
+  *placed = ChainPlaced{false, false};
+  if (l == 0) return MMAD_OK;
+  mmad_ae* h = r.h;
+  AeWS& w = r.w;
+  const int dt = h->dtype;
+  const AeLayer& a = h->L[l];
+  const AeLayer& p = h->L[l - 1];
+  LayerWS& ps = w.l[l - 1];
+  const int Mp = prows_of(w, a), Mpp = prows_of(w, p);
+  GemmEpi ep{};
+  ep.M = rows_of(w, a);
+  ep.N = a.K;
+  ep.ldo = a.Kp;
+  ep.ldpart = a.Kp;
+  const bool hop = h->vib && l == h->n_enc;
+  if (hop) {
+    ep.out = w.dzin;
+  } else if (!p.bn) {
+    ep.out = ps.dy;
+    ep.part = ps.stats;
+  } else {
+    ep.out = ps.dy;
+    ep.bn_a = ps.out;
+    ep.bn_mean = ps.mean;
+    ep.bn_rstd = ps.rstd;
+    ep.bn_part = ps.bnpart;
+    ps.bwd_fused = w.bn_mode_bwd == 2 && mmad_gemm_bn_fusable(dt, GEMM_EPI_BWD_DATA, Mp, a.Kp);
+    if (ps.bwd_fused) {
+      // BN + activation backward of layer l-1 inside this GEMM: dz directly
+      ep.out = nullptr;
+      ep.bn_sync = ps.sync_b;
+      ep.bn_err = w.bn_err;
+      ep.bn_gamma = h->params + p.g_off;
+      ep.bn_dz = ps.dz;
+      ep.bn_dgamma = h->grads + p.g_off;
+      ep.bn_dbeta = h->grads + p.be_off;
+      ep.bn_dbpart = ps.dbpart;
+      ep.bn_act = p.act;
+      ep.slope = h->slope;
+    }
+  }
+  // dz_{l-1} comes from the BN apply launch; across the VIB hop, from the
+  // reparameterisation backward, and neither event rides a launch
+  const bool apply = !hop && p.bn && !ps.bwd_fused;
+  if (!hop && done_ev && h->ev_on_kernel && !h->capturing) {
+    ep.done_ev = done_ev;
+    placed->done = true;
+  } else if (!hop && fork_below && !apply) {
+    ep.done_ev = fork_below;
+    placed->fork = true;
+  }
+  RET_IF(ae_gemm(h, w, dt, GEMM_EPI_BWD_DATA, dz_of(r, l), a.Np, weights(h, a), a.Kp, Mp, a.Kp, a.Np, ep,
+                 r.st));
+  if (hop)
+    return mmad_vib_reparam_bwd(dt, w.B, h->btl, w.k, ps.out, p.Np, w.eps, w.dzin, a.Kp, r.beta_kl,
+                                ps.dy, p.Np, ps.dbpart, r.st);
+  if (p.bn && done_ev && !placed->done) {
+    MMAD_HIP_CHECK(hipEventRecord(done_ev, r.st));
+    placed->done = true;
+  }
+  if (apply) {
+    RET_IF(mmad_bn_act_bwd_apply_ev(dt, p.act, h->slope, rows_of(w, p), p.N, Mpp, p.Np, ps.dy, ps.out,
+                                    ps.mean, ps.rstd, h->params + p.g_off, ps.bnpart, Mpp / 64, ps.dz,
+                                    h->grads + p.g_off, h->grads + p.be_off, ps.dbpart, r.st, fork_below));
+    placed->fork = fork_below != nullptr;
+  }
+  return MMAD_OK;
+}
+
+// ---- plain policy (no Adam): dW_l forks at dz_l and overlaps the chain below
+static int plain_before(BwdRun& r, int l) {
+  mmad_ae* h = r.h;
+  RET_IF(hand_off(h->ev_fork[l], r.st, r.side));
+  RET_IF(launch_dw(r, make_dw(r, l), r.side));
+  if (h->dw_events) MMAD_HIP_CHECK(hipEventRecord(h->ev_xdw[l], r.side));
+  return MMAD_OK;
+}
+static int plain_after(BwdRun& r, int l) {
+  // torch exchange: W_l is read for the last time by the bwd-data of l
+  if (r.h->dw_events && l > 0) MMAD_HIP_CHECK(hipEventRecord(r.h->ev_xdata[l], r.st));
+  return MMAD_OK;
+}
+
+// ---- data-parallel policy: dW GEMMs per exchange bucket, Adam after the exchange
+static int dp_before(BwdRun& r, int l) {
+  mmad_ae* h = r.h;
+  const DpBucket* cur = r.open_bucket();
+  const DpBucket* bk = r.closes_bucket(l);
+  // a bucket made only of the last dw_main layers of the chain runs its dW
+  // GEMMs on the main stream, idle by then, instead of behind the side
+  // stream's backlog (the exchange tail waits for them)
+  const bool on_main = cur && cur->l_hi < r.w.dw_main;
+  // below dp_fork_rows rows (host-bound steps, every event call counts) the dW
+  // GEMMs of a bucket's layers are issued together once the layer that closes
+  // it has its dz (one fork per bucket), then the bucket's event
+  // from dp_fork_rows rows the step is GPU-bound: a side-stream bucket's dW
+  // GEMMs then start at their own dz (one fork each) instead of queueing
+  // until the bucket's lowest layer
+  const bool each = h->dp_fork_rows > 0 && prows_of(r.w, h->L[l]) >= h->dp_fork_rows && cur && !on_main;
+  // (a bucket whose upper layers were below the row threshold: their dW GEMMs
+  // go first, so the bucket's event below covers them too)
+  r.pending.push_back(make_dw(r, l));
+  if (!each && !bk) return MMAD_OK;
+  hipStream_t ds = on_main ? r.st : r.side;
+  if (!on_main) RET_IF(hand_off(h->ev_fork[l], r.st, r.side));
+  RET_IF(flush(r, ds));
+  if (bk) MMAD_HIP_CHECK(hipEventRecord(h->ev_dw[l], ds));
+  return MMAD_OK;
+}
+
+// the small bucket [all bias | gamma | beta grads] + the loss: the last
+// bwd-data (just enqueued) has produced every bias partial and the loss
+// partials are the forward's: reduce them on the main stream now and queue
+// the bucket's exchange + Adam on the comm stream ahead of the remaining
+// weight buckets, so it runs while their dW GEMMs still compute instead of
+// after them
+static int dp_small_bucket(BwdRun& r) {
+  mmad_ae* h = r.h;
+  const AdamHyper* ad = r.adam;
+  RET_IF(finish_reductions(h, r.w, true, true, r.beta_kl, r.dp_loss, r.st));
+  RET_IF(hand_off(h->ev_small, r.st, h->cstream));
+  const int64_t ns = h->n_params - h->n_weight;
+  RET_IF(mmad_allreduce_pair(h->comm, h->grads + h->n_weight, ns, r.dp_loss, 1, h->cstream));
+  return mmad_adam_w(ns, h->params + h->n_weight, h->grads + h->n_weight, h->m + h->n_weight,
+                     h->v + h->n_weight, ad->w1, ad->w2, ad->eps, ad->step_size, ad->bc2_sqrt, nullptr, 0,
+                     h->cstream);
+}
+
+// exchange the bucket layer l closes (layers bk.l_hi .. l, one contiguous
+// weight range) on the comm stream as soon as its last dW GEMM is complete,
+// then its Adam update (which rewrites the bucket's weights, so it also waits
+// for the main stream's bwd-data of layer l, the last GEMM of the chain that
+// reads them)
+static int exchange_bucket(BwdRun& r, const DpBucket& bk, int l) {
+  mmad_ae* h = r.h;
+  const AdamHyper* ad = r.adam;
+  hipStream_t cs = h->cstream;
+  const bool bf16 = h->dtype == MMAD_BF16;
+  MMAD_HIP_CHECK(hipStreamWaitEvent(cs, h->ev_data[l], 0));
+  const int nr = mmad_comm_size(h->comm) > 0 ? mmad_comm_size(h->comm) : 1;
+  MMAD_HIP_CHECK(hipStreamWaitEvent(cs, h->ev_dw[l], 0));
+  const int64_t n = bk.n, boff = bk.off;
+  if (h->dp_shard && n % nr == 0 && (n / nr) % 4 == 0) {
+    // ZeRO-1 form: reduce-scatter, Adam on this rank's shard, all-gather
+    // of the updated weights the next step reads (bf16 shadow / fp32 p)
+    const int64_t cnt = n / nr, off = boff + (int64_t)mmad_comm_rank(h->comm) * cnt;
+    if (h->grad_bf16) {
+      // bf16 on the wire: round the bucket, reduce-scatter, widen this rank's slice
+      char* gb = (char*)h->grad_bf16;
+      RET_IF(mmad_to_bf16(n, h->grads + boff, gb + boff * 2, cs));
+      RET_IF(mmad_reduce_scatter_bucket_bf16(h->comm, gb + boff * 2, n, cs));
+      RET_IF(mmad_from_bf16(cnt, gb + off * 2, h->grads + off, cs));
+    } else {
+      RET_IF(mmad_reduce_scatter_bucket(h->comm, h->grads + boff, n, cs));
+    }
+    void* sh = bf16 ? (void*)((char*)h->shadow + off * 2) : nullptr;
+    RET_IF(mmad_adam_w(cnt, h->params + off, h->grads + off, h->m + off, h->v + off, ad->w1, ad->w2,
+                       ad->eps, ad->step_size, ad->bc2_sqrt, sh, bf16 ? cnt : 0, cs));
+    if (bf16)
+      RET_IF(mmad_all_gather_bucket(h->comm, (char*)h->shadow + boff * 2, n, MMAD_BF16, cs));
+    else
+      RET_IF(mmad_all_gather_bucket(h->comm, h->params + boff, n, MMAD_F32, cs));
+    if (nr > 1) h->master_stale = true;
+  } else {
+    RET_IF(mmad_allreduce_bucket(h->comm, h->grads + boff, n, cs));
+    void* sh = adam_shadow(h, h->L[l], r.w.ping);
+    RET_IF(mmad_adam_w(n, h->params + boff, h->grads + boff, h->m + boff, h->v + boff, ad->w1, ad->w2,
+                       ad->eps, ad->step_size, ad->bc2_sqrt, sh, bf16 ? n : 0, cs));
+  }
+  ++r.next_bucket;
+  return MMAD_OK;
+}
+
+// ---- fused single-GPU policy: dW_l with this layer's Adam update fused into
+// its epilogue.  It rewrites W_l, so without ping-pong shadows it starts only
+// once the main stream has finished reading W_l (bwd-data of l); the rest of
+// the chain keeps overlapping it.
+static void fused_plan_groups(BwdRun& r) {
+  mmad_ae* h = r.h;
+  if (!r.w.ping || h->capturing || h->side_hold || h->dw_group_blocks == 0) return;
+  std::vector<int> np(r.nL), kp(r.nL), rows(r.nL);
+  for (int l = 0; l < r.nL; ++l) {
+    np[l] = h->L[l].Np;
+    kp[l] = h->L[l].Kp;
+    rows[l] = prows_of(r.w, h->L[l]);
+  }
+  const int budget = h->dw_group_blocks < 0 ? mmad_gemm_group_capacity(h->dtype) : h->dw_group_blocks;
+  mmad_dw_group_plan(r.nL, np.data(), kp.data(), rows.data(), r.w.dw_main, r.nL - h->dw_late, budget,
+                     h->dw_group_members, r.grp.data());
+}
+static int fused_before(BwdRun& r, int l) {
+  // dz_l is complete: the fork of a ping-pong dW that the producing launch
+  // did not carry
+  if (r.forks_at_dz(l) && !r.fork_none(l) && !r.fork_done[l])
+    MMAD_HIP_CHECK(hipEventRecord(r.h->ev_fork[l], r.st));
+  return MMAD_OK;
+}
+static int fused_after(BwdRun& r, int l) {
+  mmad_ae* h = r.h;
+  PendingDW q = make_dw(r, l);
+  if (l < r.w.dw_main) {
+    // the last dW GEMMs of the chain go to the main stream, which is idle
+    // by then, instead of queueing behind the side stream's backlog
+    q.ep.tile_force = mmad_tile_adam_main_for(q.M, q.N, q.K) + 1;
+    return launch_dw(r, q, r.st);
+  }
+  // deferred dW GEMMs go out ahead of this one
+  r.pending.push_back(q);
+  if (h->side_hold) return MMAD_OK;   // all of them behind the chain (run_backward)
+  if (r.ping(l)) {
+    // no fork of its own: issued with the next lower layer's dW
+    if (!r.late(l) && !r.fork_ev(l)) return MMAD_OK;
+    if (r.late(l))
+      RET_IF(hand_off(h->ev_fork[l], r.st, r.side));
+    else if (!r.fork_none(l))
+      MMAD_HIP_CHECK(hipStreamWaitEvent(r.side, h->ev_fork[l], 0));
+  } else {
+    if (!r.needs_data_ev(l)) return MMAD_OK;
+    MMAD_HIP_CHECK(hipStreamWaitEvent(r.side, h->ev_data[l], 0));
+  }
+  return flush(r, r.side);
+}
+
+// backward through every layer: the chain on `st`, the dW GEMMs where the
+// policy puts them, the side stream joined back into `st` at the end
+static int run_backward(mmad_ae* h, AeWS& w, bool from_mse, float beta_kl, const AdamHyper* adam,
+                        hipStream_t st, float* dp_loss = nullptr, bool side_after_mse = false) {
+  const int nL = (int)h->L.size();
+  BwdRun r{h, w, st, h->side, adam, from_mse, side_after_mse, beta_kl, dp_loss, nL,
+           h->fork_on_kernel && !h->capturing};
+  r.fork_done.assign(nL, 0);
+  r.grp.assign(nL, -1);
+  if (r.dp()) dp_plan(h, r.plan);
+  if (r.fused()) fused_plan_groups(r);
+  const int small_at = nL > h->dp_small_at ? h->dp_small_at : 0;
+  for (int l = nL - 1; l >= 0; --l) {
+    // DP and plain issue dW_l before the bwd-data of l, fused after it
+    RET_IF(!adam ? plain_before(r, l) : r.dp() ? dp_before(r, l) : fused_before(r, l));
+    const bool need = r.needs_data_ev(l);
+    // dz_{l-1} is produced by this step: its side-stream dW fork rides on that launch
+    const bool fork_below = l > 0 && r.fork_kev && r.forks_at_dz(l - 1);
+    ChainPlaced placed;
+    RET_IF(bwd_data_step(r, l, need ? h->ev_data[l] : nullptr, fork_below ? h->ev_fork[l - 1] : nullptr,
+                         &placed));
+    if (placed.fork) r.fork_done[l - 1] = 1;
+    if (!adam) RET_IF(plain_after(r, l));
+    if (r.dp() && dp_loss && l == small_at) RET_IF(dp_small_bucket(r));
+    // ev_data[l] that the chain step could neither attach nor place ahead of a BN apply
+    if (need && !placed.done) MMAD_HIP_CHECK(hipEventRecord(h->ev_data[l], st));
+    if (r.fused()) RET_IF(fused_after(r, l));
+    if (const DpBucket* bk = r.closes_bucket(l)) RET_IF(exchange_bucket(r, *bk, l));
+  }
+  if (h->side_hold && !r.pending.empty()) {
+    RET_IF(hand_off(h->ev_hold, st, r.side));
+    RET_IF(flush(r, r.side));
+  }
+  MMAD_CHECK_ARG(r.pending.empty(), "ae backward: deferred dW GEMMs left unissued");
+  // join the side stream back into the main stream
+  return hand_off(h->ev_join, r.side, st);
 }
 
 // bias grads of every layer (when Adam did not finalise them) + the loss

@@ -18,7 +18,8 @@ pytestmark = pytest.mark.gpu
     {"side_cu_held": 32}, {"pair_rows": 0, "dw_late": 1}, {"pair_rows": 0, "dw_late": 99},
     {"pair_rows": 0, "fork_on_kernel": 0}, {"pair_rows": 0, "fork_on_kernel": 0, "ev_on_kernel": 0},
     {"pair_rows": 0, "fork_pair_below": 4}, {"pair_rows": 0, "fork_pair_below": 9},
-    {"pair_rows": 0, "fork_pair_below": 9, "fork_on_kernel": 0}])
+    {"pair_rows": 0, "fork_pair_below": 9, "fork_on_kernel": 0},
+    {"side_hold": 1}, {"pair_rows": 0, "side_hold": 1}])
 def test_schedule_knobs_match_default(knobs):
     """Every schedule knob of the fused step only reorders independent work
     across streams (event coalescing, where the loss is reduced, how many dW
@@ -42,6 +43,43 @@ def test_schedule_knobs_match_default(knobs):
     for s in range(3):
         x = torch.from_numpy(synth_windows(1024, 2048, seed=40 + s)).cuda()
         la, lb = (float(m._native.train_step_fused(x)) for m in ms)
+        assert la == lb, (s, la, lb)
+    for m in ms:
+        m._native.check_status()
+    a, b = ms[0]._native, ms[1]._native
+    for name in ("params", "exp_avg", "exp_avg_sq", "running"):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    assert torch.equal(a.shadow, b.shadow)
+    assert torch.equal(a.shadow, a.params[: a.n_weight].bfloat16())
+
+
+@pytest.mark.parametrize("knobs", [
+    {"pair_rows": 0}, {"pair_rows": 0, "fork_on_kernel": 0}, {"pair_rows": 0, "dw_late": 1},
+    {"ev_every": 1}, {"ev_on_kernel": 0}])
+def test_schedule_knobs_match_default_vib(knobs):
+    """The same comparison across the VIB hop (vib_ae, k = 1, beta_kl = 1, one
+    eps shared by both models): the bwd-data step into the bottleneck never
+    carries an attached event, so its hand-off events are always recorded
+    behind the reparameterisation backward.  Ping-pong forks on the launch and
+    behind it, a late fork, and the coalesced path's data events on the launch
+    and behind it give the default schedule's bits."""
+    import types
+    from icra2021_multimodal_ad_amd.model_builder import get_model
+    ms = []
+    for variant in (True, False):
+        cfg = types.SimpleNamespace(input_size=2048, btl_size=100, n_layers=5, gpu_id=0, dtype="bf16",
+                                    models="vib_ae", vib_k=1, beta_kl=1.0)
+        torch.manual_seed(8)
+        with _native.tune(**(knobs if variant else {})):
+            ms.append(get_model(cfg))
+    ms[1].load_state_dict(ms[0].state_dict())
+    for m in ms:
+        m._native.sync_shadow(force=True)
+    torch.manual_seed(9)
+    eps = torch.randn(1, 1024, 100, device="cuda")
+    for s in range(3):
+        x = torch.from_numpy(synth_windows(1024, 2048, seed=40 + s)).cuda()
+        la, lb = (float(m._native.train_step_fused(x, eps=eps, beta_kl=1.0, k=1)) for m in ms)
         assert la == lb, (s, la, lb)
     for m in ms:
         m._native.check_status()
