@@ -24,6 +24,51 @@ int mmad_vib_reparam_fwd_dyn(int dtype, int B, int btl, int k, const void* enc_o
                              int deterministic, void* z, int ld_z, float* kl_partial,
                              const MmadDyn* dyn, void* stream);
 
+// ---- 16-row weight-streaming operator and the online pass (mmad_skinny.hip)
+// y[16][Np] = epi(x[16][Kp] . w[Np][Kp]^T), M <= 16 valid rows (mmad_fc_rows16)
+struct MmadSkinny {
+  int M, N, Np, Kp;
+  const void* x;         // [16][Kp] (dtype), rows >= M zero
+  const void* w;         // [Np][Kp] (dtype)
+  const float* bias;     // [Np], nullable
+  int act;
+  float slope;
+  const float *scale, *shift;   // eval-BN affine [Np], nullable (both or neither)
+  void* y;               // [16][Np] (dtype), nullable; rows >= M and columns >= N written 0
+  const void* ref;       // score reference (fp32 if ref_f32, else dtype), nullable = 0
+  int ref_f32, ldref;
+  float* diff;           // fp32 [16][lddiff], nullable: columns < N, rows >= M written 0
+  int lddiff;
+  const float* colw;     // per-column weight of d^2, nullable = 1
+  float* rowsq;          // [Np/16][16], non-null selects the score epilogue
+};
+int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream);
+
+#define MMAD_ONLINE_MAX_LAYERS 32
+#define MMAD_ONLINE_MAX_DIFF 16
+// BN layers in layer order: offsets into the running-stat layout ([2][n_bn])
+// and of gamma / beta in the flat parameter buffer
+struct MmadOnlineFold {
+  int n, n_bn;
+  int bn_off[MMAD_ONLINE_MAX_LAYERS], N[MMAD_ONLINE_MAX_LAYERS];
+  int64_t g_off[MMAD_ONLINE_MAX_LAYERS], be_off[MMAD_ONLINE_MAX_LAYERS];
+};
+int mmad_online_fold(const MmadOnlineFold& f, const float* params, const float* running, float eps,
+                     float* scale, float* shift, void* stream);
+struct MmadOnlineFinish {
+  int B, n_diff;                          // valid rows, diff layers (n_enc + 1)
+  const float* rs[MMAD_ONLINE_MAX_DIFF];  // row partials [tiles][16] per diff layer
+  int tiles[MMAD_ONLINE_MAX_DIFF], widths[MMAD_ONLINE_MAX_DIFF];
+  int sap_start, sap_end;                 // clamped: 0 <= start < end <= n_diff
+  const float* nap_rs;                    // NAP row partials, null = no NAP score
+  int nap_tiles;
+  float nap_scale;                        // 1 / R
+  float* out;                             // [n_diff + 3][16]
+  uint8_t* flags;                         // [3][16], nullable
+  const float* thresholds;                // [3], nullable
+};
+int mmad_online_finish(const MmadOnlineFinish& f, void* stream);
+
 #define MMAD_MAX_REDUCE_JOBS 24
 struct MmadReduceJob {
   const float* src;   // partials, row i at src + i*stride

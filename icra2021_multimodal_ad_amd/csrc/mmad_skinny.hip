@@ -1,0 +1,271 @@
+// 16-row weight-streaming layer operator (mmad_fc_rows16) and the two small
+// kernels of the online scoring pass (mmad_ae_online_score, mmad_ae.hip).
+//
+// y[16][N] = epi(x[16][K] . W[N][K]^T) for at most 16 valid rows: the work is
+// one pass over W, so the kernel is built as a weight stream, not as a GEMM
+// tile.  One block per 16 output columns; its waves split K in interleaved
+// chunks (wave w takes chunks w, w + NW, ...: the block's loads stay
+// contiguous along each weight row); every lane loads its MFMA B fragment
+// straight from global memory with 16-byte loads, a chunk (4 loads of W, 4 of
+// x) ahead of the MFMAs that consume it, and W never passes through LDS.  The
+// waves' 16x16 fp32 accumulators meet in LDS and wave 0 adds them in wave
+// order: no atomics, no split-K slab, no barrier between blocks, so a launch's
+// bits depend on nothing but its operands.
+//
+// Fragment maps (gfx950):
+//   v_mfma_f32_16x16x32_bf16: lane l holds k = 8 (l >> 4) .. + 7 of row / column
+//     l & 15 -- one 16-byte load per operand.
+//   v_mfma_f32_16x16x4_f32: lane l holds ONE k (l >> 4) of row / column l & 15.
+//     A lane loads 4 consecutive k (16 bytes) and MFMA j takes element j of
+//     both operands' quads: k = 4 (l >> 4) + j of the 16-k step -- the same
+//     products as the natural order, summed in another, fixed order.
+//   C/D (both): column l & 15, rows 4 (l >> 4) + reg.
+#include "mmad_common.h"
+#include "mmad_ops.h"
+
+// waves per block and the weight loads' cache policy: compile-time constants
+// (DESIGN.md "Online scoring" has the measurements behind them)
+#ifndef MMAD_SKINNY_WAVES
+#define MMAD_SKINNY_WAVES 4
+#endif
+#ifndef MMAD_SKINNY_NT
+#define MMAD_SKINNY_NT 0
+#endif
+
+namespace {
+
+constexpr int NW = MMAD_SKINNY_WAVES;
+constexpr int U = 4;   // 16-byte loads per operand and chunk
+
+template <typename T> struct Frag;
+template <> struct Frag<bf16> { typedef bf16x8 V; static constexpr int KL = 8; };
+template <> struct Frag<float> { typedef floatx4 V; static constexpr int KL = 4; };
+
+template <typename V> __device__ __forceinline__ V load_w(const V* p) {
+#if MMAD_SKINNY_NT
+  return __builtin_nontemporal_load(p);
+#else
+  return *p;
+#endif
+}
+
+__device__ __forceinline__ void mma(floatx4& acc, const bf16x8 (&a)[U], const bf16x8 (&b)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b[u], acc, 0, 0, 0);
+}
+__device__ __forceinline__ void mma(floatx4& acc, const floatx4 (&a)[U], const floatx4 (&b)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][j], acc, 0, 0, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(NW * 64) void skinny_k(const MmadSkinny a) {
+  typedef typename Frag<T>::V V;
+  constexpr int KL = Frag<T>::KL;   // k per lane and load
+  constexpr int CK = 4 * KL * U;    // k per chunk: 128 (bf16) / 64 (fp32) = 256 bytes of a row
+  __shared__ floatx4 red[NW][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c16 = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * 16;
+  const T* wp = (const T*)a.w + (size_t)(n0 + c16) * a.Kp + g * KL;
+  const T* xp = (const T*)a.x + (size_t)c16 * a.Kp + g * KL;
+  const int nch = a.Kp / CK;
+  floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+  V bw[U], ax[U];
+  int c = wv;
+  if (c < nch) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bw[u] = load_w((const V*)(wp + (size_t)c * CK + u * 4 * KL));
+      ax[u] = *(const V*)(xp + (size_t)c * CK + u * 4 * KL);
+    }
+  }
+  while (c < nch) {
+    V bn[U], an[U];
+    const int cn = c + NW;
+    const bool more = cn < nch;   // wave-uniform
+    if (more) {   // the next chunk's loads fly over this chunk's MFMAs
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        bn[u] = load_w((const V*)(wp + (size_t)cn * CK + u * 4 * KL));
+        an[u] = *(const V*)(xp + (size_t)cn * CK + u * 4 * KL);
+      }
+    }
+    mma(acc, ax, bw);
+    if (!more) break;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bw[u] = bn[u];
+      ax[u] = an[u];
+    }
+    c = cn;
+  }
+  red[wv][lane] = acc;
+  __syncthreads();
+  if (wv != 0) return;
+  floatx4 s = red[0][lane];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) s += red[w][lane];
+
+  // ---- epilogue: column n, rows 4 g + r
+  const int n = n0 + c16;
+  const bool nv = n < a.N;
+  const float b = a.bias ? a.bias[n] : 0.f;
+  const float sc = a.scale ? a.scale[n] : 1.f;
+  const float sh = a.shift ? a.shift[n] : 0.f;
+  const float cw = a.colw ? a.colw[n] : 1.f;
+  float sq[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = 4 * g + r;
+    const bool valid = nv && m < a.M;
+    float v = apply_act(s[r] + b, a.act, a.slope);
+    if (a.scale) v = v * sc + sh;
+    v = valid ? v : 0.f;
+    if (a.y) ((T*)a.y)[(size_t)m * a.Np + n] = from_f32<T>(v);
+    sq[r] = 0.f;
+    if (a.rowsq) {
+      float rf = 0.f;
+      if (a.ref && valid)
+        rf = a.ref_f32 ? ((const float*)a.ref)[(size_t)m * a.ldref + n]
+                       : to_f32<T>(((const T*)a.ref)[(size_t)m * a.ldref + n]);
+      const float d = v - rf;   // invalid: 0 - 0
+      if (a.diff && nv) a.diff[(size_t)m * a.lddiff + n] = d;
+      sq[r] = d * d * cw;
+    }
+  }
+  if (a.rowsq) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) sq[r] += __shfl_xor(sq[r], o);
+      if (c16 == 0) a.rowsq[(size_t)blockIdx.x * 16 + 4 * g + r] = sq[r];
+    }
+  }
+}
+
+// eval-BN (scale, shift) of every BN layer in one grid (mmad_bn_eval_affine
+// per layer): element j of the [n_bn] running-stat layout
+__global__ __launch_bounds__(256) void online_fold_k(const MmadOnlineFold f, const float* __restrict__ params,
+                                                     const float* __restrict__ running, float eps,
+                                                     float* __restrict__ scale, float* __restrict__ shift) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= f.n_bn) return;
+  int i = 0;
+  while (i + 1 < f.n && j >= f.bn_off[i + 1]) ++i;
+  const int c = j - f.bn_off[i];
+  float s = 0.f, t = 0.f;
+  if (c < f.N[i]) {
+    s = params[f.g_off[i] + c] * (float)(1.0 / sqrt((double)running[f.n_bn + j] + (double)eps));
+    t = params[f.be_off[i] + c] - running[j] * s;
+  }
+  scale[j] = s;
+  shift[j] = t;
+}
+
+// one block: the row partials summed in tile order, BASE / SAP / NAP and flags
+__global__ __launch_bounds__(320) void online_finish_k(const MmadOnlineFinish f) {
+  __shared__ float lsq[MMAD_ONLINE_MAX_DIFF + 1][16];
+  const int j = threadIdx.x >> 4, b = threadIdx.x & 15;
+  if (j <= f.n_diff && (j < f.n_diff || f.nap_rs)) {
+    const float* p = j < f.n_diff ? f.rs[j] : f.nap_rs;
+    const int nt = j < f.n_diff ? f.tiles[j] : f.nap_tiles;
+    float s = 0.f;
+    int t = 0;
+    for (; t + 8 <= nt; t += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(t + u) * 16 + b];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; t < nt; ++t) s += p[(size_t)t * 16 + b];
+    lsq[j][b] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x >= 16 || b >= f.B) return;
+  float* out = f.out;
+  for (int l = 0; l < f.n_diff; ++l) out[l * 16 + b] = lsq[l][b];
+  const float base = lsq[0][b] / (float)f.widths[0];
+  float ss = 0.f;
+  int wsum = 0;
+  for (int l = f.sap_start; l < f.sap_end; ++l) {
+    ss += lsq[l][b];
+    wsum += f.widths[l];
+  }
+  const float sap = ss / (float)wsum;
+  out[f.n_diff * 16 + b] = base;
+  out[(f.n_diff + 1) * 16 + b] = sap;
+  float nap = 0.f;
+  if (f.nap_rs) {
+    nap = lsq[f.n_diff][b] * f.nap_scale;
+    out[(f.n_diff + 2) * 16 + b] = nap;
+  }
+  if (f.flags) {
+    // strict >: get_f1_score's prediction rule; a NaN threshold compares false
+    const float* th = f.thresholds;
+    f.flags[b] = th ? (uint8_t)(base > th[0]) : 0;
+    f.flags[16 + b] = th ? (uint8_t)(sap > th[1]) : 0;
+    f.flags[32 + b] = (th && f.nap_rs) ? (uint8_t)(nap > th[2]) : 0;
+  }
+}
+
+}  // namespace
+
+int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream) {
+  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16, "fc_rows16: dtype %d (MMAD_F32 or MMAD_BF16)", dtype);
+  MMAD_CHECK_ARG(a.M >= 1 && a.M <= 16, "fc_rows16: M=%d outside 1..16", a.M);
+  MMAD_CHECK_ARG(a.N >= 1 && a.N <= a.Np && a.Np % 16 == 0 && a.Kp >= MMAD_PAD && a.Kp % MMAD_PAD == 0,
+                 "fc_rows16: bad sizes N=%d Np=%d Kp=%d (Np a multiple of 16, Kp of %d)", a.N, a.Np, a.Kp,
+                 MMAD_PAD);
+  MMAD_CHECK_ARG(a.x && a.w && ((uintptr_t)a.x | (uintptr_t)a.w) % 16 == 0,
+                 "fc_rows16: x and w must be non-null and 16-byte aligned");
+  MMAD_CHECK_ARG(a.y || a.rowsq, "fc_rows16: neither y nor rowsq to write");
+  MMAD_CHECK_ARG(a.rowsq || (!a.ref && !a.diff && !a.colw), "fc_rows16: ref / diff / colw need rowsq");
+  if (a.act < MMAD_ACT_NONE || a.act > MMAD_ACT_TANH) {
+    mmad_set_error("fc_rows16: activation %d has no per-element epilogue", a.act);
+    return MMAD_EUNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == MMAD_BF16)
+    skinny_k<bf16><<<a.Np / 16, NW * 64, 0, s>>>(a);
+  else
+    skinny_k<float><<<a.Np / 16, NW * 64, 0, s>>>(a);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
+int mmad_fc_rows16(int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
+                   const float* bias, int act, float slope, const float* bn_scale, const float* bn_shift,
+                   void* y, const void* ref, int ref_dtype, int ldref, float* diff, int lddiff,
+                   const float* colw, float* rowsq, void* stream) {
+  MMAD_CHECK_ARG(K >= 1 && K <= Kp, "fc_rows16: K=%d outside 1..Kp=%d", K, Kp);
+  MMAD_CHECK_ARG(!bn_scale == !bn_shift, "fc_rows16: bn_scale and bn_shift go together");
+  MMAD_CHECK_ARG(!ref || ((ref_dtype == MMAD_F32 || ref_dtype == dtype) && ldref >= N),
+                 "fc_rows16: ref is fp32 or the operand dtype, ldref >= N");
+  MMAD_CHECK_ARG(!diff || lddiff >= N, "fc_rows16: lddiff < N");
+  MmadSkinny a{};
+  a.M = M; a.N = N; a.Np = Np; a.Kp = Kp;
+  a.x = x; a.w = w; a.bias = bias; a.act = act; a.slope = slope;
+  a.scale = bn_scale; a.shift = bn_shift; a.y = y;
+  a.ref = ref; a.ref_f32 = ref_dtype == MMAD_F32; a.ldref = ldref;
+  a.diff = diff; a.lddiff = lddiff; a.colw = colw; a.rowsq = rowsq;
+  return mmad_skinny_launch(dtype, a, stream);
+}
+
+int mmad_online_fold(const MmadOnlineFold& f, const float* params, const float* running, float eps,
+                     float* scale, float* shift, void* stream) {
+  if (f.n_bn == 0) return MMAD_OK;
+  online_fold_k<<<(f.n_bn + 255) / 256, 256, 0, (hipStream_t)stream>>>(f, params, running, eps, scale, shift);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
+int mmad_online_finish(const MmadOnlineFinish& f, void* stream) {
+  MMAD_CHECK_ARG(f.n_diff >= 1 && f.n_diff <= MMAD_ONLINE_MAX_DIFF, "online_finish: %d diff layers", f.n_diff);
+  online_finish_k<<<1, 320, 0, (hipStream_t)stream>>>(f);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}

@@ -520,6 +520,46 @@ class NativeAE:
              ptr(out["v"]), ptr(out["mu_s"]), ptr(out["var"]), sp, sb, ws, need, stream_ptr())
         return out, state
 
+    def online_state(self):
+        """A state buffer for online_score (mmad_ae_online_state_bytes): uint8
+        on this device, sized for the handle as it stands (dtype, attached
+        fit); the caller keeps it and passes it to every call."""
+        need = int(self._lib.mmad_ae_online_state_bytes(self._h))
+        if need < 0:
+            raise _native.NativeError("online state size query failed")
+        return torch.zeros(need + 256, dtype=torch.uint8, device=self.device)
+
+    def online_score(self, x, B, out, state, flags=None, thresholds=None, start=0, end=None,
+                     graph=True):
+        """Scores of B <= 16 windows now (mmad_ae_online_score): x fp32 [>=B, D]
+        on this device, out fp32 [n_enc+4, 16] (layer_sq rows, BASE, SAP, NAP),
+        flags uint8 [3, 16] and thresholds fp32 [3] optional device tensors,
+        state from online_state().  With graph=True a repeated call (the same
+        tensors) replays one captured hipGraph."""
+        self._require(x)
+        if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or \
+                x.shape[1] != self.enc_widths[0]:
+            raise ValueError("online_score: x must be row-major fp32 [>=B, D] on the model device")
+        if int(B) > x.shape[0]:
+            raise ValueError(f"online_score: B={B} > the {x.shape[0]} rows of x")
+        if out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() \
+                or tuple(out.shape) != (self.n_enc + 4, 16):
+            raise ValueError("online_score: out must be contiguous fp32 [n_enc+4, 16] on the model device")
+        if flags is not None and (flags.device != self.device or flags.dtype != torch.uint8
+                                  or not flags.is_contiguous() or tuple(flags.shape) != (3, 16)):
+            raise ValueError("online_score: flags must be contiguous uint8 [3, 16] on the model device")
+        if thresholds is not None and (thresholds.device != self.device or thresholds.dtype != torch.float32
+                                       or not thresholds.is_contiguous() or thresholds.numel() != 3):
+            raise ValueError("online_score: thresholds must be contiguous fp32 [3] on the model device")
+        self.sync_shadow()
+        base = state.data_ptr()
+        aligned = (base + 255) // 256 * 256
+        end = self.n_enc + 2 if end is None else int(end)
+        call("mmad_ae_online_score", self._h, ptr(x), x.stride(0), int(B), int(start), end,
+             ptr(thresholds), ptr(out), ptr(flags), ctypes.c_void_p(aligned),
+             state.numel() - (aligned - base), 1 if graph else 0, stream_ptr())
+        return out
+
     def diff_widths(self):
         return [self.enc_widths[0]] + self.enc_widths[1:]
 

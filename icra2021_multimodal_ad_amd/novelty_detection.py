@@ -154,6 +154,42 @@ class NoveltyDetecter:
             del nm
         return out
 
+    def online_scorer(self, model, train_x, valid_x):
+        """The deployment form of ``scores``: an online.OnlineScorer over
+        ``model`` that returns BASE, SAP and NAP of up to 16 windows per call
+        from one replayed graph.  NAP is fitted on ``train_x`` as ``scores``
+        fits it (``config.nap_fit_stream`` honoured); for a bf16 model the
+        whole online path runs on the fp32 twin of ``_nap_model`` (NAP needs
+        fp32 diffs and one graph is to produce all three scores).  The
+        thresholds are calibrated on ``valid_x`` (metric.threshold_metrics'
+        quantile rule on the batch route's validation scores).  Single
+        process."""
+        from .online import OnlineScorer
+        cfg = self.config
+        model.eval()
+        start = getattr(cfg, "start_layer_index", 0)
+        end = cfg.n_layers + 1 - getattr(cfg, "end_layer_index", -1)
+        with torch.no_grad():
+            nm = _nap_model(model, cfg)
+            nat = nm._native
+            widths = nat.diff_widths()
+            n = len(widths)
+            nap = NapScorer(nm, start_layer_index=start, end_layer_index=end)
+            layers = (nap.sel.start, min(nap.sel.stop, n))
+            cuts = np.cumsum([0] + widths)
+            sel = slice(int(cuts[layers[0]]), int(cuts[layers[1]]))
+            if bool(getattr(cfg, "nap_fit_stream", False)):
+                nap.fit_stream(nm, train_x, cfg.batch_size, layers=layers)
+            else:
+                nap.fit(train_diffs=_device_diffs(nm, train_x, cfg.batch_size)[:, sel].contiguous())
+            # (the layout scores() reduces: the same validation scores to the bit)
+            lv = _layer_sq(nm, valid_x, 698).t().contiguous().t()
+            valid = {"base": base_from_layer_sq(lv, widths), "sap": sap_from_layer_sq(lv, widths, start, end),
+                     "nap": nap.score(_device_diffs(nm, valid_x, 698)[:, sel])}
+            scorer = OnlineScorer(nm, nap=nap, start_layer_index=start, end_layer_index=end)
+            scorer.calibrate(valid)
+        return scorer
+
     def test(self, model, dset_manager, train_loader, valid_loader, test_loader, df_test=None):
         """novelty_detection.py:15-85.  Returns ((base_auroc, base_aupr),
         (sap_auroc, sap_aupr), (nap_auroc, nap_aupr), df_test) with df_test a

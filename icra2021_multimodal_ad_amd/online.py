@@ -1,0 +1,113 @@
+"""Online scoring: the anomaly scores of the latest few windows, now.
+
+The reference's deployment loop (test_file/realtime_tester.py:291-309,
+get_realtime_dataloader) fuses the latest 10 sensor windows and asks for their
+scores, over and over.  ``OnlineScorer`` is the object that loop calls: it owns
+a fixed device input buffer [16, D], the outputs, the threshold buffer and the
+native state (mmad_ae_online_state_bytes), so every call after the first is one
+replayed hipGraph of about 20 short weight-streaming launches
+(mmad_ae_online_score; DESIGN.md §4 "Online scoring").  More than 16 windows
+are the batch route's (reconstruction_aggregation.score_windows).
+"""
+import numpy as np
+import torch
+
+from . import metric
+
+ROWS = 16
+METHODS = ("base", "sap", "nap")
+
+
+class OnlineScorer:
+    def __init__(self, model, nap=None, start_layer_index=0, end_layer_index=None, thresholds=None):
+        """model: an eval-mode autoencoder of the plugin surface (fp32 or bf16,
+        no split-bf16 score planes).  nap: a fitted NapScorer (its fit is
+        attached to ``model`` for this object's lifetime; a standalone scorer
+        is taken to cover the SAP layer range) or None (no NAP score).
+        start / end_layer_index: the SAP layer range as
+        ``sap_from_layer_sq`` takes it.  thresholds: {'base','sap','nap'} ->
+        float, or None (NaN: no flag until ``calibrate``)."""
+        nat = model._native
+        model.eval()
+        self.model, self.nat, self.nap = model, nat, nap
+        n = nat.n_enc + 1
+        self.start = int(start_layer_index)
+        self.end = n + 1 if end_layer_index is None else int(end_layer_index)
+        if nap is not None:
+            layers = None
+            if nap.model is None:          # standalone: name the layers it was fit on
+                s = min(max(self.start, 0), n - 1)
+                e = min(max(self.end, s + 1), n)
+                layers = (s, e)
+            nap.attach(model, precision="f32", layers=layers)
+        dev = nat.device
+        self.x = torch.zeros((ROWS, nat.enc_widths[0]), device=dev)
+        self.out = torch.zeros((nat.n_enc + 4, ROWS), device=dev)
+        self.flags = torch.zeros((3, ROWS), device=dev, dtype=torch.uint8)
+        self.thresholds = torch.full((3,), float("nan"), device=dev)
+        self.state = nat.online_state()
+        if thresholds is not None:
+            self.set_thresholds(thresholds)
+
+    def set_thresholds(self, thresholds):
+        """{'base','sap','nap'} -> float (a missing one: NaN, no flag), written
+        into the device buffer the pass reads: the next replay sees them."""
+        t = torch.tensor([float(thresholds.get(k, float("nan"))) for k in METHODS], dtype=torch.float32)
+        self.thresholds.copy_(t)
+        return t
+
+    def calibrate(self, valid_scores, q=metric.F1_QUANTILE):
+        """Thresholds by the quantile rule of metric.threshold_metrics
+        (np.quantile(valid, q), linear) on validation scores {'base','sap','nap'}
+        -> [Nv]; returns them as a dict."""
+        thr = {}
+        for k in METHODS:
+            v = valid_scores.get(k)
+            if v is not None:
+                v = torch.as_tensor(v).reshape(-1)
+                thr[k] = metric.threshold_metrics(v, v[:1], np.zeros(1, np.uint8), q)[0]
+        self.set_thresholds(thr)
+        return thr
+
+    def _run(self, B):
+        n_enc = self.nat.n_enc
+        self.nat.online_score(self.x, B, self.out, self.state, flags=self.flags,
+                              thresholds=self.thresholds, start=self.start, end=self.end)
+        return {"layer_sq": self.out[:n_enc + 1, :B], "base": self.out[n_enc + 1, :B],
+                "sap": self.out[n_enc + 2, :B],
+                "nap": self.out[n_enc + 3, :B] if self.nap is not None else None,
+                "flags": self.flags[:, :B]}
+
+    def score(self, x):
+        """x: [B <= 16, D], host or device.  Returns {'base','sap','nap',
+        'layer_sq','flags'}: views of this object's fixed outputs on the
+        device, rewritten by the next call (copy what you keep)."""
+        x = torch.as_tensor(x)
+        x = x.reshape(x.shape[0], -1)
+        B = x.shape[0]
+        if B > ROWS:
+            raise ValueError(f"OnlineScorer.score: {B} windows > {ROWS}; score_windows "
+                             "(reconstruction_aggregation) is the batch route")
+        if B < 1 or x.shape[1] != self.x.shape[1]:
+            raise ValueError(f"OnlineScorer.score: x must be [1..{ROWS}, {self.x.shape[1]}], got {tuple(x.shape)}")
+        self.x[:B].copy_(x, non_blocking=True)
+        return self._run(B)
+
+    def score_frames(self, hsr_net, r, d, t, m):
+        """One step of get_realtime_dataloader: HSR_Net.forward (mmad_hsr_fuse)
+        of the latest ``hsr_net.batch_size`` <= 16 frames straight into the
+        fixed input buffer, on the same stream, then ``score``'s pass."""
+        B = int(hsr_net.batch_size)
+        if B > ROWS:
+            raise ValueError(f"OnlineScorer.score_frames: slicing_size {B} > {ROWS}; score_windows "
+                             "(reconstruction_aggregation) is the batch route")
+        fused = hsr_net.forward(r, d, None, t, m, out=self.x)
+        if fused.reshape(B, -1).shape[1] != self.x.shape[1]:
+            raise ValueError("OnlineScorer.score_frames: the fused row width is not the model's input size")
+        return self._run(B)
+
+    def close(self):
+        """Detach the fit from the model."""
+        if self.nap is not None:
+            self.nap.detach()
+            self.nap = None

@@ -198,6 +198,27 @@ int mmad_fc_fwd_score(int dtype, int M, int N, int K, int Mp, int Np, int Kp, co
                       const float* bn_scale, const float* bn_shift, void* y, const void* ref,
                       float* rowsq, float* diff, int ld_diff, void* stream);
 
+/* FCLayer.forward for at most 16 rows, as a weight stream (the online scoring
+ * path's layer operator; no reference counterpart): one block per 16 output
+ * columns reads its rows of w once, straight into MFMA fragments.
+ *   y[16][Np] = bn_affine(act(x[16][Kp] . w[Np][Kp]^T + bias[Np]))
+ * x: packed [16][Kp] of dtype (MMAD_F32 / MMAD_BF16), rows >= M zero, w as
+ * mmad_fc_fwd takes it, both 16-byte aligned; Kp a multiple of 128, Np of 16;
+ * M in 1..16.  y (nullable): rows >= M and columns >= N are written 0.
+ * rowsq non-null selects the score epilogue: d = y - ref on the fp32 value of
+ * y (ref nullable = 0; ref_dtype MMAD_F32 or dtype; row stride ldref; only
+ * rows < M, columns < N are read), rowsq fp32 [Np/16][16] = per 16-column tile
+ * and row the sum of colw[n] d^2 (colw nullable = 1) over the tile's columns
+ * < N, rows >= M zero; diff (nullable, fp32 [16][lddiff]): d for the columns
+ * < N of all 16 rows, rows >= M as 0, nothing else.  With ref = NULL, act
+ * none and colw this is the NAP run's GEMM (mmad_nap_score, K = W, N = R).
+ * Activations: none, LeakyReLU, ReLU, sigmoid, tanh.  The result depends on
+ * the operands alone (fixed summation order, no atomics). */
+int mmad_fc_rows16(int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
+                   const float* bias, int act, float slope, const float* bn_scale,
+                   const float* bn_shift, void* y, const void* ref, int ref_dtype, int ldref,
+                   float* diff, int lddiff, const float* colw, float* rowsq, void* stream);
+
 /* BatchNorm1d eval affine (layers/fc_layer.py:33): scale = gamma/sqrt(rv+eps),
  * shift = beta - rm*scale, for N columns (padded columns -> 0). */
 int mmad_bn_eval_affine(int N, int Np, const float* gamma, const float* beta, const float* rm,
@@ -715,6 +736,42 @@ int mmad_ae_nap_fit_stream(mmad_ae* h, int start, int end, const float* x, int l
                            void* fit_state, int64_t fit_bytes, void* ws, int64_t ws_bytes,
                            void* stream);
 
+/* Online scoring: the scores of B <= 16 windows now (the deployment loop,
+ * test_file/realtime_tester.py:291-309), as about 20 short weight-streaming
+ * launches (mmad_fc_rows16 per layer) instead of the batch path's 128-row
+ * tiles.  state: a caller-owned, 256-byte aligned device buffer of
+ * mmad_ae_online_state_bytes(h) bytes (-1: null handle; a pure function of the
+ * handle's layers, dtype and attached fit, independent of
+ * mmad_ae_workspace_bytes) holding the packed input, every layer's 16-row
+ * outputs, the folded BN constants, the row partials and, with a fit
+ * attached, the packed NAP operand [16][Kp] (its padding zeroed when the
+ * handle first sees the buffer; valid columns rewritten by every call, rows
+ * >= B as zero).
+ * x fp32 [B][ld_x] (device).  out fp32 [n_enc + 4][16]: rows 0..n_enc =
+ * layer_sq as mmad_ae_score, then BASE = layer_sq[0] / D, SAP = the mean of
+ * d^2 over the diff layers [sap_start, sap_end) with the reference's clamping
+ * (utils/metric.py:155-171), and NAP -- written only with an MMAD_F32 fit
+ * attached (mmad_ae_set_nap; its own layer range), else left untouched.
+ * Columns >= B of every row are left untouched.  flags (nullable) uint8
+ * [3][16]: flag[m][b] = score_m[b] > thresholds[m] for BASE, SAP, NAP (the
+ * strict > of get_f1_score's prediction rule; 0 for a NaN threshold, for
+ * thresholds == NULL and for NAP without a fit); thresholds fp32 [3] in
+ * device memory, read when the pass runs.
+ * use_graph != 0: the first call for a given (x, ld_x, B, range, out, flags,
+ * thresholds, state, weight buffer, fit) runs eagerly and captures; later
+ * calls are one hipGraphLaunch (up to 8 cached per handle, counted by
+ * mmad_ae_graph_count and dropped by mmad_ae_clear_graphs, attach / detach
+ * with the score graphs).  Weights, BN running statistics, the fit's vt / bias
+ * / w and the thresholds are read at replay time.
+ * MMAD_EINVAL, nothing launched: B outside 1..16, a null or too small state,
+ * an unbound handle, score planes attached (mmad_ae_score_dtype ==
+ * MMAD_BF16X3: split-bf16 planes are not supported on this path) or an
+ * MMAD_BF16X3 fit attached. */
+int64_t mmad_ae_online_state_bytes(const mmad_ae* h);
+int mmad_ae_online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
+                         const float* thresholds, float* out, uint8_t* flags, void* state,
+                         int64_t state_bytes, int use_graph, void* stream);
+
 /* Split-K health of the executor workspace `ws` (as mmad_gemm_status): a
  * no-op returning MMAD_OK unless split-K is enabled (tuning knob 4 > 1);
  * otherwise synchronises `stream` and returns MMAD_EHIP if any GEMM combine
@@ -743,7 +800,8 @@ int mmad_ae_probe_read(mmad_ae* h, float* ms, int max_n);
  * (mmad_gemm_pair_kernel, MMAD_DW_PAIR). */
 int mmad_ae_probe_layers(const mmad_ae* h);
 
-/* number of cached score graphs (-1 for a null handle); drop them all */
+/* number of cached score graphs, online passes included (-1 for a null
+ * handle); drop them all */
 int mmad_ae_graph_count(const mmad_ae* h);
 int mmad_ae_clear_graphs(mmad_ae* h);
 

@@ -1,0 +1,166 @@
+"""Latency of scoring a few windows now: the batch path's entry points against
+the online path (mmad_ae_online_score) -> profiles/online_latency.json.
+
+Workload: the D = 2048, btl 100, 5-layer autoencoder, fp32 and bf16 handles,
+B = 10 and 16 windows, a full-range fp32 NAP fit attached (W = R = 6442; the
+fit's values are random but finite -- only the time matters here).  After 50
+warm-up calls, median and 10th / 90th percentile of 300 calls, alternated in
+one process, each as GPU time between two events and as host wall including
+one stream synchronise:
+  (a) mmad_ae_score_nap, eager
+  (b) mmad_ae_score_nap_stream with N = batch = B, use_graph = 1
+  (c) mmad_ae_online_score, replayed
+  (c0) the same without a fit (no NAP launch)
+Beside them the weight-stream lower bound: the bytes every pass has to read
+once (AE weights + the encoder again + V^T) / 8 TB/s.
+
+  python tools/online_latency.py [--out profiles/online_latency.json]
+  python tools/online_latency.py --variant TAG --out FILE   # (c) / (c0) only, merged
+      into FILE under "variants": a library built with other compile-time
+      constants (MMAD_LIB=...: -DMMAD_SKINNY_NT=1, -DMMAD_SKINNY_WAVES=8)"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+import types
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from icra2021_multimodal_ad_amd import _native  # noqa: E402
+from icra2021_multimodal_ad_amd._native import pad, ptr, stream_ptr  # noqa: E402
+
+WARMUP, CALLS = 50, 300
+HBM_BYTES_PER_S = 8e12
+
+
+def build(dtype):
+    from icra2021_multimodal_ad_amd.model_builder import get_model
+    cfg = types.SimpleNamespace(input_size=2048, btl_size=100, n_layers=5, gpu_id=0, dtype=dtype, models="ae")
+    torch.manual_seed(3)
+    m = get_model(cfg)
+    m.eval()
+    return m
+
+
+def random_fit(nat):
+    W = nat.diff_width()
+    R, Kp, Rp = W, pad(W), pad(W)
+    g = torch.Generator(device="cuda").manual_seed(7)
+    vt = torch.zeros((Rp, Kp), device="cuda")
+    vt[:R, :W] = torch.randn((R, W), device="cuda", generator=g) / W ** 0.5
+    bias = torch.zeros(Rp, device="cuda")
+    bias[:R] = 0.1 * torch.randn(R, device="cuda", generator=g)
+    w = torch.zeros(Rp, device="cuda")
+    w[:R] = torch.rand(R, device="cuda", generator=g) + 0.5
+    return R, vt, bias, w
+
+
+def stream_bytes(nat, with_nap):
+    e = 2 if nat.dtype_name == "bf16" else 4
+    ae = sum(L["Np"] * L["Kp"] for L in nat.layers) * e
+    enc = sum(L["Np"] * L["Kp"] for L in nat.layers[:nat.n_enc]) * e
+    vt = pad(nat.diff_width()) ** 2 * 4 if with_nap else 0
+    return ae + enc + vt
+
+
+def measure(fns):
+    """fns: {name: callable enqueueing one call on the current stream}."""
+    st = torch.cuda.current_stream()
+    ev = {k: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for k in fns}
+    gpu, wall = {k: [] for k in fns}, {k: [] for k in fns}
+    for it in range(WARMUP + CALLS):
+        for k, fn in fns.items():
+            a, b = ev[k]
+            t0 = time.perf_counter()
+            a.record(st)
+            fn()
+            b.record(st)
+            st.synchronize()
+            t1 = time.perf_counter()
+            if it >= WARMUP:
+                gpu[k].append(a.elapsed_time(b) * 1e3)
+                wall[k].append((t1 - t0) * 1e6)
+
+    def stats(v):
+        p = np.percentile(np.asarray(v), [50, 10, 90])
+        return {"median_us": float(p[0]), "p10_us": float(p[1]), "p90_us": float(p[2])}
+    return {k: {"gpu": stats(gpu[k]), "wall": stats(wall[k])} for k in fns}
+
+
+def run_case(dtype, B, variant):
+    lib = _native.load()
+    m = build(dtype)
+    nat = m._native
+    h, s = nat._h, stream_ptr()
+    D, n = nat.enc_widths[0], nat.n_enc
+    x = torch.randn((16, D), device="cuda")
+    out = torch.zeros((n + 4, 16), device="cuda")
+    flags = torch.zeros((3, 16), device="cuda", dtype=torch.uint8)
+    thr = torch.ones(3, device="cuda")
+    nat.sync_shadow()
+
+    def online(state):
+        base = state.data_ptr()
+        al = (base + 255) // 256 * 256
+        args = (h, ptr(x), D, B, 0, n + 2, ptr(thr), ptr(out), ptr(flags), ctypes.c_void_p(al),
+                state.numel() - (al - base), 1, s)
+
+        def fn():
+            _native.check(lib.mmad_ae_online_score(*args), "mmad_ae_online_score")
+        return fn
+
+    res = {}
+    state0 = nat.online_state()
+    res.update(measure({"c0_online_no_nap": online(state0)}))
+    fit = random_fit(nat)
+    nat.set_nap(fit)
+    state1 = nat.online_state()
+    fns = {"c_online": online(state1)}
+    if not variant:
+        ws, nb = nat.workspace(B, 1)
+        lsq = torch.zeros((n + 1, B), device="cuda")
+        nap = torch.zeros(B, device="cuda")
+        a_args = (h, ptr(x), D, B, ptr(lsq), ptr(nap), ws, nb, s)
+        b_args = (h, ptr(x), D, B, B, ptr(lsq), B, ptr(nap), ws, nb, 1, s)
+        fns = {"a_score_nap_eager": lambda: _native.check(lib.mmad_ae_score_nap(*a_args), "a"),
+               "b_score_nap_stream_graph": lambda: _native.check(lib.mmad_ae_score_nap_stream(*b_args), "b"),
+               "c_online": fns["c_online"]}
+    res.update(measure(fns))
+    assert torch.isfinite(out[:, :B]).all()
+    res["weight_stream_bound_us"] = {"with_nap": stream_bytes(nat, True) / HBM_BYTES_PER_S * 1e6,
+                                     "no_nap": stream_bytes(nat, False) / HBM_BYTES_PER_S * 1e6}
+    nat.set_nap(None)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/online_latency.json")
+    ap.add_argument("--variant", default=None)
+    a = ap.parse_args()
+    _native.require_gpu()
+    cases = {f"{dt}_B{B}": run_case(dt, B, a.variant) for dt in ("f32", "bf16") for B in (10, 16)}
+    if a.variant:
+        doc = json.load(open(a.out))
+        doc.setdefault("variants", {})[a.variant] = {"lib": os.path.basename(os.environ.get("MMAD_LIB", "")), "cases": cases}
+    else:
+        doc = {"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "calls": CALLS,
+               "hbm_bytes_per_s": HBM_BYTES_PER_S, "cases": cases}
+        for k, c in cases.items():
+            b, cc = c["b_score_nap_stream_graph"]["gpu"]["median_us"], c["c_online"]["gpu"]["median_us"]
+            c["online_vs_b_gpu"] = cc / b
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    for k, c in cases.items():
+        print(k, {n_: (round(v["gpu"]["median_us"], 1), round(v["wall"]["median_us"], 1))
+                  for n_, v in c.items() if isinstance(v, dict) and "gpu" in v})
+
+
+if __name__ == "__main__":
+    main()
