@@ -16,22 +16,13 @@
 //   up in its epilogue (s[k] acc + t[k] db[n]), runs on a side stream with that
 //   layer's Adam update fused into the epilogue (single-GPU step), overlapping
 //   the remaining backward chain on the main stream.
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+//
+// This file: the handle's lifecycle, the workspace, the eval forward and the
+// training executor.  The score path is mmad_ae_score.hip, the 16-row online
+// path mmad_ae_online.hip; mmad_ae_impl.h holds what the three share.
+#include "mmad_ae_impl.h"
 
-#include "mmad_common.h"
-#include "mmad_gemm.h"
-#include "mmad_ops.h"
-#include "mmad_comm.h"
-
-#define RET_IF(x)                    \
-  do {                               \
-    int r_ = (x);                    \
-    if (r_ != MMAD_OK) return r_;    \
-  } while (0)
+using namespace mmad_ae_impl;
 
 // Executor events only order work between streams of this device, so they
 // skip the system-scope fence (L2 writeback for host visibility) that a
@@ -43,286 +34,6 @@ static unsigned ev_flags(int sysfence) {
   return sysfence ? (unsigned)hipEventDisableTiming
                   : (unsigned)(hipEventDisableTiming | hipEventDisableSystemFence);
 }
-
-struct AeLayer {
-  int K, N, Kp, Np;
-  int act, bn, enc;
-  int64_t w_off, b_off, g_off, be_off, bn_off;
-};
-
-struct mmad_ae {
-  int dtype, n_enc, n_dec, vib, btl;
-  float slope, bn_eps, bn_mom;
-  std::vector<AeLayer> L;
-  int64_t n_params, n_weight, n_bn;
-  float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *running = nullptr;
-  void* shadow = nullptr;
-  // bf16 ping-pong: the fused step's Adam writes the new weights into
-  // shadow_alt while this step's backward still reads shadow, then the two
-  // swap; so a dW GEMM need not wait for its layer's bwd-data GEMM
-  void* shadow_alt = nullptr;
-  // split-bf16 scoring (mmad_ae_set_score_planes, F32 handles): bf16
-  // [2][n_weight] weight planes; the eval forward / score GEMMs then run as
-  // MMAD_BF16X3.  planes_stale: the fp32 weights were (or may have been)
-  // written since the last split; the scoring entry points re-split first
-  void* planes = nullptr;
-  bool planes_stale = true;
-  // streamed NAP (mmad_ae_set_nap): the fit of the concatenated diffs of the
-  // diff layers [start, end) (0 = x_hat - x, 1 + e = encoder layer e), all
-  // caller-owned.  dtype: the NAP GEMM's (MMAD_F32: fp32 operand written
-  // through the score GEMMs' diff output; MMAD_BF16X3: plane operand written
-  // through their diff-plane output, vt split into vt_planes at attach)
-  struct NapFit {
-    bool on = false;
-    int start = 0, end = 0, K = 0, Kp = 0, R = 0, Rp = 0, dtype = MMAD_F32;
-    const float *vt = nullptr, *bias = nullptr, *w = nullptr;
-    void* vt_planes = nullptr;
-  } nap;
-  // side stream + events for the dW / Adam overlap (created at bind time)
-  hipStream_t side = nullptr;
-  std::vector<hipEvent_t> ev_fork, ev_data;
-  hipEvent_t ev_join = nullptr;
-  hipEvent_t ev_loss = nullptr;   // fused step: forward done -> the loss reduction on the side stream
-  // the schedule, copied from the tune table at create (include/mmad.h knobs
-  // 16-27): one schedule per handle, whatever the table says later
-  unsigned ev_flags_ = 0;
-  int loss_side = 1;      // knob 23: reduce the loss on the side stream after the forward
-  int side_prio_hi = 0;   // knob 26
-  // knob 15: > 0 = the side stream is created behind a CU mask that leaves
-  // this many CUs (evenly spaced over the mask) to the main stream alone
-  int side_cu_held = 0;
-  // data-parallel step: the small bucket (bias / gamma / beta grads + loss)
-  // goes on the comm stream right after the bwd-data GEMM of this layer
-  // (ahead of this layer's and the lower layers' weight buckets); knob 24
-  int dp_small_at = 1;
-  // data-parallel step: sharded weight buckets (knob 28); master_stale: the
-  // bf16 model's fp32 master weights / every model's Adam moments are
-  // current only on their owning rank since the last mmad_ae_dp_sync_master
-  int dp_shard = 1;
-  // data-parallel step: consecutive layers' weight gradients (backward
-  // order) share one exchange bucket until it holds at least dp_bucket_mib
-  // MiB of fp32 gradient (knob 30; 0 = one bucket per layer)
-  int dp_bucket_mib = 8;
-  // data-parallel step: from this many padded rows each side-stream dW GEMM
-  // is issued as soon as its own dz is complete instead of with its bucket's
-  // closing layer (knob 14; 0 = one fork per bucket)
-  int dp_fork_rows = 1024;
-  bool master_stale = false;
-  int mse_tiles = 0;   // loss partials written by the last MSE GEMM
-  // data parallelism: RCCL communicator (not owned), its stream and events
-  mmad_comm* comm = nullptr;
-  hipStream_t cstream = nullptr;
-  std::vector<hipEvent_t> ev_dw;
-  // torch-exchange data parallelism (mmad_ae_dw_events): the forward+backward
-  // without Adam records ev_xdw[l] after dW_l and ev_xdata[l] after bwd-data of
-  // l.  System-scope fences (unlike the executor's own events): the exchange
-  // may read the gradients with a copy engine, which does not see the L2
-  bool dw_events = false;
-  std::vector<hipEvent_t> ev_xdw, ev_xdata;
-  // optional bf16 gradient exchange (mmad_ae_set_grad_bf16): n_weight bf16
-  void* grad_bf16 = nullptr;
-  hipEvent_t ev_small = nullptr, ev_cdone = nullptr;
-  // schedule study (knob 29): every side-stream dW + Adam GEMM held until the
-  // main stream has enqueued the whole bwd-data chain (ev_hold), to separate
-  // the chain's in-step contention from its barrier costs
-  int side_hold = 0;
-  // knob 33 (ping-pong steps): the side-stream dW + Adam GEMMs of the top
-  // dw_late layers fork behind the layer's bwd-data + BN apply instead of at
-  // its dz, so the largest dW does not share the CUs with the apply below it
-  int dw_late = 0;
-  // knob 34 (ping-pong steps): each side-stream dW's fork event (dz_l ready)
-  // completed by the launch that produces dz_l (the BN-backward apply or the
-  // bwd-data GEMM: hipExtLaunchKernel stop event) instead of a marker packet
-  // recorded on the main stream before the bwd-data GEMM of l -- each marker
-  // held the main stream's next dispatch ~5 us; the top layer's fork is the
-  // loss reduction's wait on the MSE launch, already on the side stream
-  int fork_on_kernel = 1;
-  // knob 35 (ping-pong steps): from this layer down, side-stream dW GEMMs
-  // fork in pairs -- every other layer's dz gets no fork event and its dW is
-  // issued with the next lower layer's (where the side stream lags the chain
-  // by more than a layer anyway, each fork saved is a ~5-us hold on the
-  // main stream; 0 = every layer forks)
-  int fork_pair_below = 0;
-  // ping-pong steps (mmad_ae_set_dw_group): consecutive side-stream layers
-  // whose dW + Adam GEMM takes the 64x64 tile are issued as ONE grouped launch
-  // (mmad_gemm_dispatch_group) at the lowest member's fork -- at 4096 rows
-  // each of the narrow layers' launches is one block's 64-stage K loop,
-  // 23-25 us for 16 to 135 blocks, and they ran back to back.  blocks = the
-  // group's budget of padded blocks (0 = off: every dW its own launch; < 0 =
-  // one resident round of the kernel), members = at most this many per group
-  int dw_group_blocks = MMAD_DW_GROUP_BLOCKS_DEFAULT;
-  int dw_group_members = MMAD_GEMM_GROUP_MAX;
-  hipEvent_t ev_hold = nullptr;
-  // fused step: dW GEMMs of layers < dw_main run on the caller's stream
-  // (knob 19; tools/sched_sweep.py: 0.499 ms (2) vs 0.512 (1) vs 0.523 (3));
-  // keep_grads (knob 25): also write dW to the grads buffer
-  int dw_main = 2;
-  // ping-pong schedule per call from this many padded rows (bf16 with a
-  // shadow pair; knob 20), with dw_main_ping main-stream dW GEMMs (knob 21):
-  // VIB B=4096 0.941-0.945 vs 0.995-0.999 ms/step, B=1024 0.450-0.455 vs
-  // 0.442-0.449 (profiles/r02bu_*, r02bv_*)
-  int pair_rows = 4096;
-  int dw_main_ping = 1;
-  int keep_grads = 0;
-  // train-mode BN: fold the batch statistics into the consumer's weights
-  // (bn_fold_k; the bf16 throughput path) or normalise the activations into y
-  // (bn_train_apply_k; the exact-fp32 parity path: folding contracts the raw,
-  // un-centred activations and cancels the mean back out, which costs the
-  // fp32 path ~10x the reference's rounding error on BN-producer layers).
-  // Set at create from the dtype and knob 16.
-  int fold = 1;
-  // train-mode BN inside the producing GEMM (bn_mode 2, MMAD_BN_MODE): the
-  // forward GEMM's epilogue finishes the batch statistics and writes y, the
-  // bwd-data GEMM's epilogue writes dz (a per-column-tile barrier between the
-  // blocks of one column, mmad_gemm_mfma.hip) -- no finalize / fold / apply
-  // launches.  Layers whose grid cannot be co-resident fall back to mode 0
-  // (apply kernels).  0 = apply kernels, 1 = fold, 2 = fused (knob 16).  Default: bf16
-  // 2 up to bn_fused_rows padded rows per call (measured: D=2048 B=1024
-  // 0.495 ms/step fused vs 0.531 apply vs 0.536 fold; B=4096 VIB 1.33 fused
-  // vs 1.32 apply vs 1.27 fold -- more tiles per column, longer barrier
-  // waits), fold above; fp32 0 (the parity path).
-  int bn_mode = 0;
-  // backward BN schedule override for the bf16 path (knob 17: -1 =
-  // the forward's; 2 = fused into the bwd-data GEMMs whatever the forward did:
-  // the fused backward needs only a, the saved mean / rstd and gamma, which
-  // every forward schedule leaves)
-  int bn_mode_bwd = -1;
-  int bn_fused_rows = 2048;   // knob 18
-  // fused step: record the "bwd-data of l done" event only every ev_every-th
-  // side-stream layer (each record costs a bubble on the main stream); the dW
-  // GEMMs of the layers in between wait for the next recorded one (knob 22;
-  // c2 0.435-0.440 vs 0.442-0.444 with 1, profiles/r02bv_*)
-  int ev_every = 2;
-  // the main stream's hand-off events (bwd-data -> side-stream dW, MSE ->
-  // side-stream loss) completed by the GEMM launch itself (knob 31)
-  int ev_on_kernel = 1;
-  // hipGraph cache for mmad_ae_score_stream: one captured graph per
-  // (input, output, workspace, N, batch) pass, replayed with one launch
-  struct ScoreGraph {
-    const float* x; int64_t ld_x, N; int batch; float* sq; int64_t ld_sq; void* ws;
-    const void* wts;   // weight operand base (the bf16 shadow may be re-pointed)
-    float* nap;        // NAP output (null: a pass without it) and the fit it was captured with
-    const void* nap_vt;
-    hipGraphExec_t exec;
-  };
-  std::vector<ScoreGraph> graphs;
-  hipStream_t gstream = nullptr;   // capture stream (the caller's may be the null stream)
-  // the same for mmad_ae_online_score: one captured 16-row pass per call
-  // signature.  online_ready: the state buffer whose NAP operand this handle
-  // has zeroed (its padding is never written again)
-  struct OnlineGraph {
-    const float* x; int ld_x, B, sap_start, sap_end; const float* thr; float* out; uint8_t* flags;
-    void* state; const void* wts; const void* nap_vt;
-    hipGraphExec_t exec;
-  };
-  std::vector<OnlineGraph> ographs;
-  const void* online_ready = nullptr;
-  // kernel probe (mmad_ae_probe): timing events around ONE GEMM launch of
-  // the step, on the stream it is launched on (bench roofline, in situ)
-  mutable int probe_id = -1;
-  mutable int probe_n = 0;
-  mutable unsigned probe_mask = 0;    // layers the last probed launch covered (bit l)
-  std::vector<hipEvent_t> probe_ev;   // [2 * capacity]: start, end pairs
-  hipEvent_t probe_sync = nullptr;    // a main-stream probe's start waits for the side stream
-  // probe kinds 2 / 3: the events ride on the launch itself (hipExtLaunchKernel
-  // start / stop: the kernel's own start and end, as rocprofv3's kernel records)
-  // and nothing waits for the side stream -- the launch as it runs in the
-  // step's schedule, so the probe can stay on through a timed region
-  bool probe_kev = false;
-  // hipGraph-captured fused train steps (mmad_ae_train_step_graph): one per
-  // call signature, replayed after a host->device copy of the per-call values
-  // (a ring of pinned host slots, each reused only once its copy has run)
-  struct TrainGraph {
-    int B, k, ld_x, xvec, has_eps, dw_main, ev_every, keep_grads;
-    const void* ws;
-    const void* shadow;   // the bf16 shadow the captured kernels read / write
-    float beta_kl, b1, b2, aeps;
-    hipGraphExec_t exec;
-  };
-  std::vector<TrainGraph> tgraphs;
-  static constexpr int kDynSlots = 64;
-  MmadDyn* dyn_host = nullptr;
-  hipEvent_t dyn_ev[kDynSlots] = {};
-  bool dyn_used[kDynSlots] = {};
-  int dyn_next = 0;
-  bool capturing = false;
-  bool graph_broken = false;
-  // workspace whose split-K control block this handle has zeroed
-  const void* ws_zeroed = nullptr;
-  void clear_train_graphs() {
-    for (auto& g : tgraphs) (void)hipGraphExecDestroy(g.exec);
-    tgraphs.clear();
-  }
-  ~mmad_ae() {
-    clear_train_graphs();
-    for (auto e : dyn_ev)
-      if (e) (void)hipEventDestroy(e);
-    if (dyn_host) (void)hipHostFree(dyn_host);
-    for (auto e : probe_ev) (void)hipEventDestroy(e);
-    if (probe_sync) (void)hipEventDestroy(probe_sync);
-    for (auto& g : graphs) (void)hipGraphExecDestroy(g.exec);
-    for (auto& g : ographs) (void)hipGraphExecDestroy(g.exec);
-    if (gstream) (void)hipStreamDestroy(gstream);
-    for (auto e : ev_fork) (void)hipEventDestroy(e);
-    for (auto e : ev_data) (void)hipEventDestroy(e);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (ev_hold) (void)hipEventDestroy(ev_hold);
-    if (ev_loss) (void)hipEventDestroy(ev_loss);
-    for (auto e : ev_dw) (void)hipEventDestroy(e);
-    for (auto e : ev_xdw) (void)hipEventDestroy(e);
-    for (auto e : ev_xdata) (void)hipEventDestroy(e);
-    if (ev_small) (void)hipEventDestroy(ev_small);
-    if (ev_cdone) (void)hipEventDestroy(ev_cdone);
-    if (cstream) (void)hipStreamDestroy(cstream);
-    if (side) (void)hipStreamDestroy(side);
-  }
-};
-
-struct LayerWS {
-  void *out, *y, *dy, *dz;
-  float *stats, *mean, *rstd, *scale, *shift, *dbpart, *rowsq;
-  float* ref32;     // x3 scoring: fp32 copy of an encoder layer's pass-1 output (else null)
-  double* bnpart;   // fp64 BN-backward column partials [Mp/64][2][Np]
-  // consumer of a train-mode BN producer: W*scale (GEMM dtype) and the
-  // per-64-column partials of sum_k shift[k] W[n][k]
-  void* wf;
-  float* cpart;
-  // this call: BN of the layer fused into its forward GEMM / into the
-  // bwd-data GEMM of the next layer (bias gradient partials per 64 rows)
-  bool fwd_fused, bwd_fused;
-  unsigned* sync_f;   // fused-BN barrier counters (MMAD_BN_SYNC_WORDS each)
-  unsigned* sync_b;
-};
-struct AeWS {
-  int B, k, Mpe, Mpd;
-  MmadDyn* dyn_dev = nullptr;    // device slot for the per-call values (graph-captured step)
-  const MmadDyn* dyn = nullptr;  // set: kernels read x / loss / noise / Adam terms from dyn_dev
-  void *xin, *zbuf, *dzin;
-  float *eps, *klpart, *misc, *lossp;
-  int64_t kl_parts;
-  // split-K workspace per stream (0 = caller's stream, 1 = side stream);
-  // the two control blocks are contiguous (one memset per call)
-  float* sk_slab[2];
-  unsigned* sk_ctl[2];
-  size_t sk_ctl_bytes;   // both split-K control blocks + the fused-BN counters
-  unsigned* bn_err;      // fused-BN barrier timeout word
-  int bn_mode;           // this call's train-mode BN schedule (0 apply, 1 fold, 2 fused)
-  int bn_mode_bwd;       // ... of the backward (2: fused into the bwd-data GEMMs; else the apply kernel)
-  // this call's fused-step schedule: ping-pong the bf16 weight shadows (the
-  // Adam of layer l writes the shadow the NEXT step reads, so dW_l waits only
-  // for dz_l) and how many of the last dW GEMMs run on the main stream
-  bool ping = false;
-  int dw_main = 2;
-  std::vector<LayerWS> l;
-  // streamed NAP (a fit attached, else null): the packed operand [Mpe][nap.Kp]
-  // (fp32, or bf16 planes [2][Mpe][nap.Kp]) and the NAP GEMM's row partials
-  void* nap_x = nullptr;
-  float* nap_rowsq = nullptr;
-  int64_t nap_x_off = -1;   // byte offset of nap_x in the workspace
-  int64_t bytes;
-};
-
-static size_t esz(int dtype) { return dtype == MMAD_BF16 ? 2 : 4; }
 
 // can the dispatcher choose a split-K factor > 1 for this handle's GEMMs?
 // (any dtype: a forced override, knob 4; bf16: the dW rule, when a dW
@@ -336,7 +47,7 @@ static bool splitk_possible(int dtype) {
   return mmad_splitk_dw_override() > 1 || mmad_splitk_dw_blocks() > 0;
 }
 
-static void carve(const mmad_ae* h, int B, int k, char* base, AeWS& w) {
+void mmad_ae_impl::carve(const mmad_ae* h, int B, int k, char* base, AeWS& w) {
   int64_t off = 0;
   auto take = [&](int64_t bytes) -> char* {
     off = (off + 255) / 256 * 256;
@@ -557,7 +268,7 @@ int mmad_ae_bind(mmad_ae* h, float* params, float* grads, float* adam_m, float* 
                  void* shadow, float* running) {
   MMAD_CHECK_ARG(h && params, "ae_bind: null params");
   MMAD_CHECK_ARG(h->dtype != MMAD_BF16 || shadow, "ae_bind: bf16 needs a shadow buffer");
-  h->clear_train_graphs();   // captured steps bake the buffer addresses in
+  h->tgraphs.clear();   // captured steps bake the buffer addresses in
   h->params = params;
   h->grads = grads;
   h->m = adam_m;
@@ -615,87 +326,12 @@ int mmad_ae_set_shadow_pair(mmad_ae* h, void* alt) {
 
 const void* mmad_ae_current_shadow(const mmad_ae* h) { return h ? h->shadow : nullptr; }
 
-// dtype of the eval forward / score GEMMs
-static int score_dt(const mmad_ae* h) { return h->planes ? MMAD_BF16X3 : h->dtype; }
-
 // re-split the weight region into the score planes if a weight write may have
 // happened since the last split (one launch on the caller's stream)
-static int refresh_planes(mmad_ae* h, hipStream_t st, bool force = false) {
+int mmad_ae_impl::refresh_planes(mmad_ae* h, hipStream_t st, bool force) {
   if (!h->planes || !(h->planes_stale || force)) return MMAD_OK;
   RET_IF(mmad_split_planes(h->n_weight, h->params, h->planes, (char*)h->planes + h->n_weight * 2, st));
   h->planes_stale = false;
-  return MMAD_OK;
-}
-
-int mmad_ae_set_score_planes(mmad_ae* h, void* planes) {
-  MMAD_CHECK_ARG(h, "ae_set_score_planes: null handle");
-  MMAD_CHECK_ARG(h->dtype == MMAD_F32, "ae_set_score_planes: fp32 handles only (a bf16 handle "
-                 "scores on its own shadow)");
-  MMAD_CHECK_ARG(((uintptr_t)planes) % 16 == 0, "ae_set_score_planes: planes must be 16-byte aligned");
-  h->planes = planes;
-  h->planes_stale = true;
-  return mmad_ae_clear_graphs(h);   // captured passes bake the operand dtype and addresses in
-}
-
-int mmad_ae_score_dtype(const mmad_ae* h) { return h ? score_dt(h) : -1; }
-
-// first column of diff layer j in the concatenated diffs (j = n_enc + 1: their width)
-static int diff_col(const mmad_ae* h, int j) {
-  int c = 0;
-  for (int i = 0; i < j; ++i) c += i == 0 ? h->L[0].K : h->L[i - 1].N;
-  return c;
-}
-
-int mmad_ae_set_nap(mmad_ae* h, int start, int end, int R, const float* vt, const float* bias,
-                    const float* w, int dtype, void* vt_planes, void* stream) {
-  MMAD_CHECK_ARG(h, "ae_set_nap: null handle");
-  if (!vt) {   // detach
-    if (h->nap.on) {
-      h->nap = mmad_ae::NapFit{};
-      return mmad_ae_clear_graphs(h);
-    }
-    return MMAD_OK;
-  }
-  MMAD_CHECK_ARG(start >= 0 && end > start && end <= h->n_enc + 1,
-                 "ae_set_nap: bad layer range [%d, %d) of %d diff layers", start, end, h->n_enc + 1);
-  MMAD_CHECK_ARG(R >= 1 && bias && w, "ae_set_nap: bad fit (R=%d, null bias / w)", R);
-  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16X3,
-                 "ae_set_nap: the NAP GEMM runs as MMAD_F32 or MMAD_BF16X3 (dtype %d)", dtype);
-  mmad_ae::NapFit f;
-  f.on = true;
-  f.start = start;
-  f.end = end;
-  f.K = diff_col(h, end) - diff_col(h, start);
-  f.Kp = mmad_roundup(f.K, MMAD_PAD);
-  f.R = R;
-  f.Rp = mmad_roundup(R, MMAD_PAD);
-  f.dtype = dtype;
-  f.vt = vt;
-  f.bias = bias;
-  f.w = w;
-  if (dtype == MMAD_BF16X3) {
-    MMAD_CHECK_ARG(score_dt(h) == MMAD_BF16X3, "ae_set_nap: an MMAD_BF16X3 NAP GEMM needs score planes "
-                   "attached (mmad_ae_set_score_planes): its operand is written by the x3 score GEMMs");
-    MMAD_CHECK_ARG(vt_planes && ((uintptr_t)vt_planes) % 16 == 0 && ((uintptr_t)vt) % 16 == 0,
-                   "ae_set_nap: MMAD_BF16X3 needs 16-byte aligned vt and vt_planes");
-    f.vt_planes = vt_planes;
-    const int64_t n = (int64_t)f.Rp * f.Kp;
-    RET_IF(mmad_split_planes(n, vt, vt_planes, (char*)vt_planes + n * 2, stream));
-  }
-  h->nap = f;
-  return mmad_ae_clear_graphs(h);   // captured passes bake the operand layout and the fit's addresses in
-}
-
-int mmad_ae_nap_operand(const mmad_ae* h, int B, int64_t* info) {
-  MMAD_CHECK_ARG(h && info && B >= 1, "ae_nap_operand: bad arguments");
-  MMAD_CHECK_ARG(h->nap.on, "ae_nap_operand: no NAP fit attached");
-  AeWS w;
-  carve(h, B, 1, nullptr, w);
-  info[0] = w.nap_x_off;
-  info[1] = w.Mpe;
-  info[2] = h->nap.Kp;
-  info[3] = h->nap.K;
-  info[4] = h->nap.dtype;
   return MMAD_OK;
 }
 
@@ -713,13 +349,13 @@ static void* adam_shadow(const mmad_ae* h, const AeLayer& a, bool ping) {
 }
 
 // ---------------------------------------------------------------------------
-static const void* weights(const mmad_ae* h, const AeLayer& a) {
+const void* mmad_ae_impl::weights(const mmad_ae* h, const AeLayer& a) {
   if (h->dtype == MMAD_BF16) return (const char*)h->shadow + a.w_off * 2;
   return h->params + a.w_off;
 }
 // the weight operand of an eval / score GEMM of dtype dt: for MMAD_BF16X3 the
 // layer's hi plane, with its lo plane (n_weight elements on) set in ep
-static const void* weights_dt(const mmad_ae* h, const AeLayer& a, int dt, GemmEpi& ep) {
+const void* mmad_ae_impl::weights_dt(const mmad_ae* h, const AeLayer& a, int dt, GemmEpi& ep) {
   if (dt != MMAD_BF16X3) return weights(h, a);
   ep.b_lo = (const char*)h->planes + (h->n_weight + a.w_off) * 2;
   return (const char*)h->planes + a.w_off * 2;
@@ -728,8 +364,8 @@ static const void* weights_dt(const mmad_ae* h, const AeLayer& a, int dt, GemmEp
 // input of layer l; in train mode a BN producer's output stays pre-BN (a): the
 // forward reads it against the folded weights, the dW GEMM fixes up with
 // (scale, shift) in its epilogue
-static const void* input_of(const mmad_ae* h, const AeWS& w, int l, bool train,
-                            const float** scale, const float** shift) {
+const void* mmad_ae_impl::input_of(const mmad_ae* h, const AeWS& w, int l, bool train,
+                                   const float** scale, const float** shift) {
   *scale = *shift = nullptr;
   if (l == 0) return w.xin;
   if (h->vib && l == h->n_enc) return w.zbuf;
@@ -743,8 +379,8 @@ static const void* input_of(const mmad_ae* h, const AeWS& w, int l, bool train,
 }
 
 
-static int prepare_ws(const mmad_ae* h, int B, int k, void* ws, int64_t ws_bytes, AeWS& w,
-                      hipStream_t st) {
+int mmad_ae_impl::prepare_ws(const mmad_ae* h, int B, int k, void* ws, int64_t ws_bytes, AeWS& w,
+                             hipStream_t st) {
   MMAD_CHECK_ARG(B >= 1 && k >= 1, "bad batch B=%d k=%d", B, k);
   MMAD_CHECK_ARG(h->vib || k == 1, "k>1 needs the VIB head");
   carve(h, B, k, (char*)ws, w);
@@ -773,7 +409,6 @@ static int prepare_ws(const mmad_ae* h, int B, int k, void* ws, int64_t ws_bytes
 // PROBE_DW + layer (its dW GEMM, with the fused Adam in the fused step)
 enum { PROBE_FWD = 0, PROBE_DW = 64 };
 
-// GEMM dispatch with the split-K workspace of the stream it runs on
 // data-parallel weight buckets: walking the layers in backward order,
 // consecutive layers join one bucket until it holds >= dp_bucket_mib MiB of
 // fp32 gradient (layer 0 always closes the last).  The weights are one
@@ -804,9 +439,10 @@ static void dp_plan(const mmad_ae* h, std::vector<DpBucket>& out) {
   }
 }
 
-static int ae_gemm(const mmad_ae* h, const AeWS& w, int dt, int epi, const void* A, int lda,
-                   const void* B, int ldb, int Mp, int Np, int K, GemmEpi ep, hipStream_t s,
-                   int* cfg = nullptr, int probe = -1) {
+// GEMM dispatch with the split-K workspace of the stream it runs on
+int mmad_ae_impl::ae_gemm(const mmad_ae* h, const AeWS& w, int dt, int epi, const void* A, int lda,
+                          const void* B, int ldb, int Mp, int Np, int K, GemmEpi ep, hipStream_t s,
+                          int* cfg, int probe) {
   const int r = (h->side && s == h->side) ? 1 : 0;
   ep.sk_slab = w.sk_slab[r];
   ep.sk_ctl = w.sk_ctl[r];
@@ -927,15 +563,8 @@ static int ae_gemm_group(const mmad_ae* h, const AeWS& w, int dt, const PendingD
   return MMAD_OK;
 }
 
-static inline int rows_of(const AeWS& w, const AeLayer& a) { return a.enc ? w.B : w.B * w.k; }
-static inline int prows_of(const AeWS& w, const AeLayer& a) { return a.enc ? w.Mpe : w.Mpd; }
-static float* running_mean(const mmad_ae* h, const AeLayer& a) { return h->running + a.bn_off; }
-static float* running_var(const mmad_ae* h, const AeLayer& a) {
-  return h->running + h->n_bn + a.bn_off;
-}
-
-static GemmEpi fwd_epi(const mmad_ae* h, const AeWS& w, const AeLayer& a, const LayerWS& s,
-                       int M, void* out, bool folded) {
+GemmEpi mmad_ae_impl::fwd_epi(const mmad_ae* h, const AeWS& w, const AeLayer& a, const LayerWS& s,
+                              int M, void* out, bool folded) {
   GemmEpi ep{};
   ep.M = M;
   ep.N = a.N;
@@ -1650,52 +1279,30 @@ int mmad_ae_train_step_graph(mmad_ae* h, const float* x, int ld_x, int B, int k,
   MMAD_HIP_CHECK(hipEventRecord(h->dyn_ev[slot], st));
   h->dyn_used[slot] = true;
   const int xvec = ((uintptr_t)x % 16 == 0 && ld_x % 4 == 0) ? 1 : 0;
-  for (auto& g : h->tgraphs) {
-    if (g.B == B && g.k == k && g.ld_x == ld_x && g.xvec == xvec && g.has_eps == (eps != nullptr) &&
-        g.ws == ws && g.shadow == h->shadow && g.dw_main == h->dw_main && g.ev_every == h->ev_every &&
-        g.keep_grads == h->keep_grads && g.beta_kl == beta_kl && g.b1 == beta1 && g.b2 == beta2 &&
-        g.aeps == adam_eps) {
-      MMAD_HIP_CHECK(hipGraphLaunch(g.exec, st));
-      return MMAD_OK;
-    }
+  const TrainKey key{B, k, ld_x, xvec, eps != nullptr, h->dw_main, h->ev_every, h->keep_grads, ws,
+                     h->shadow, beta_kl, beta1, beta2, adam_eps};
+  if (hipGraphExec_t hit = h->tgraphs.find(key)) {
+    MMAD_HIP_CHECK(hipGraphLaunch(hit, st));
+    return MMAD_OK;
   }
   // first call of this signature: run it eagerly (reading the same device
   // slot; this also settles every GEMM tile choice, which cannot be timed
   // under capture), then capture the identical launch sequence
   w.dyn = w.dyn_dev;
-  RET_IF(run_forward(h, w, x, ld_x, 0, eps, seed, offset, st));
-  RET_IF(run_backward(h, w, true, beta_kl, &ah, st));
-  RET_IF(finish_reductions(h, w, false, true, beta_kl, loss_out, st));
-  if (!h->gstream) MMAD_HIP_CHECK(hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking));
-  hipGraph_t graph = nullptr;
-  if (hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    h->graph_broken = true;
-    (void)hipGetLastError();
-    return MMAD_OK;
-  }
-  h->capturing = true;
-  int rc = run_forward(h, w, x, ld_x, 0, eps, seed, offset, h->gstream);
-  if (rc == MMAD_OK) rc = run_backward(h, w, true, beta_kl, &ah, h->gstream);
-  if (rc == MMAD_OK) rc = finish_reductions(h, w, false, true, beta_kl, loss_out, h->gstream);
-  h->capturing = false;
-  const hipError_t ec = hipStreamEndCapture(h->gstream, &graph);
+  auto pass = [&](hipStream_t s) {
+    RET_IF(run_forward(h, w, x, ld_x, 0, eps, seed, offset, s));
+    RET_IF(run_backward(h, w, true, beta_kl, &ah, s));
+    return finish_reductions(h, w, false, true, beta_kl, loss_out, s);
+  };
+  RET_IF(pass(st));
   hipGraphExec_t exec = nullptr;
-  hipError_t ei = hipErrorUnknown;
-  if (rc == MMAD_OK && ec == hipSuccess && graph)
-    ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  if (graph) (void)hipGraphDestroy(graph);
-  if (rc != MMAD_OK || ec != hipSuccess || ei != hipSuccess) {
+  if (capture_graph(h, pass, &exec).stage != GC_OK) {
     // this step already ran eagerly; later calls stay eager
     h->graph_broken = true;
     (void)hipGetLastError();
     return MMAD_OK;
   }
-  if (h->tgraphs.size() >= 16) {
-    (void)hipGraphExecDestroy(h->tgraphs.front().exec);
-    h->tgraphs.erase(h->tgraphs.begin());
-  }
-  h->tgraphs.push_back({B, k, ld_x, xvec, eps != nullptr, h->dw_main, h->ev_every, h->keep_grads, ws,
-                        h->shadow, beta_kl, beta1, beta2, adam_eps, exec});
+  h->tgraphs.insert(key, exec);
   return MMAD_OK;
 }
 
@@ -1854,322 +1461,6 @@ int mmad_ae_forward(mmad_ae* h, const float* x, int ld_x, int B, int train_bn, f
   return MMAD_OK;
 }
 
-// one batch of the scoring pass on a prepared workspace; layer_sq row l at
-// layer_sq + l*ld_sq
-// nap (nullable; needs a fit and no caller diffs): the in-range score GEMMs
-// write their diffs straight into the packed NAP operand, then the NAP GEMM
-// and its column sum write nap[0..B)
-// fit (nullable, without nap; the streaming NAP fit): the diffs of its layers
-// go, as fp32, into its own packed operand and nothing else changes
-struct DiffSink {
-  int start, end, K, Kp;   // diff layers [start, end), their width and its padding
-  bool x3;                 // bf16 plane operand (the attached fit's x3 NAP GEMM)
-  void* x;                 // [Mpe][Kp]
-};
-static int score_batch(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq,
-                       int64_t ld_sq, float* diffs, AeWS& w, hipStream_t st, float* nap = nullptr,
-                       const DiffSink* fit = nullptr) {
-  // x3 (score planes attached): activations travel as bf16 planes, every
-  // reference of a diff stays fp32 -- pass 1 leaves an fp32 copy of each
-  // encoder output (ref32), the decoder's last layer scores against the
-  // caller's x itself, and the SCORE epilogue subtracts before it rounds
-  const int dt = score_dt(h);
-  const bool x3 = dt == MMAD_BF16X3;
-  const int nL = (int)h->L.size();
-  RET_IF(mmad_pack_input(dt, B, h->L[0].K, w.Mpe, h->L[0].Kp, x, ld_x, w.xin, st));
-  int ld_diff = h->L[0].K;
-  for (int e = 0; e < h->n_enc; ++e) ld_diff += h->L[e].N;
-  const mmad_ae::NapFit& nf = h->nap;
-  const bool nap_x3 = nap && nf.dtype == MMAD_BF16X3;
-  const bool routed = nap || fit;
-  const DiffSink sk = nap ? DiffSink{nf.start, nf.end, nf.K, nf.Kp, nap_x3, w.nap_x}
-                          : (fit ? *fit : DiffSink{});
-  // route diff layer j's diffs into the operand (columns relative to the range's first)
-  auto nap_route = [&](GemmEpi& ep, int j) {
-    if (!routed || j < sk.start || j >= sk.end) return;
-    const int col = diff_col(h, j) - diff_col(h, sk.start);
-    if (sk.x3) {
-      ep.dp_hi = sk.x;
-      ep.dp_lo = (char*)sk.x + (size_t)w.Mpe * sk.Kp * 2;
-      ep.lddp = sk.Kp;
-      ep.dp_col = col;
-    } else {
-      ep.diff = (float*)sk.x + col;
-      ep.lddiff = sk.Kp;
-    }
-  };
-  // the operand's padding, every batch: a ragged batch's workspace is carved
-  // at other offsets than the full batches', so nothing survives from them
-  if (routed)
-    RET_IF(mmad_zero_pad(sk.x3 ? 2 : 4, sk.x3 ? 2 : 1, B, sk.K, w.Mpe, sk.Kp, sk.x, st));
-  // pass 1: eval forward; the decoder's last layer scores d0 = x_hat - x
-  for (int l = 0; l < nL; ++l) {
-    const AeLayer& a = h->L[l];
-    LayerWS& s = w.l[l];
-    const int M = rows_of(w, a), Mp = prows_of(w, a);
-    const float *isc, *ish;
-    const void* in = input_of(h, w, l, false, &isc, &ish);
-    GemmEpi ep = fwd_epi(h, w, a, s, M, a.bn ? s.y : s.out, false);
-    if (a.bn) {
-      RET_IF(mmad_bn_eval_affine(a.N, a.Np, h->params + a.g_off, h->params + a.be_off,
-                                 running_mean(h, a), running_var(h, a), h->bn_eps, s.scale,
-                                 s.shift, st));
-      ep.bn_scale = s.scale;
-      ep.bn_shift = s.shift;
-    }
-    const void* wt = weights_dt(h, a, dt, ep);
-    if (l == nL - 1) {
-      ep.ref = x3 ? (const void*)x : w.xin;
-      ep.ldref = x3 ? ld_x : a.Np;
-      ep.rowsq = s.rowsq;
-      ep.ldrow = Mp;
-      ep.diff = diffs;
-      ep.lddiff = ld_diff;
-      nap_route(ep, 0);
-      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_SCORE, in, a.Kp, wt, a.Kp, Mp, a.Np, a.Kp, ep, st));
-    } else {
-      if (x3 && a.enc) {
-        ep.out32 = s.ref32;
-        ep.ld32 = a.Np;
-      }
-      RET_IF(ae_gemm(h, w, dt, GEMM_EPI_FWD, in, a.Kp, wt, a.Kp, Mp, a.Np, a.Kp, ep, st));
-    }
-    if (h->vib && l == h->n_enc - 1) {
-      RET_IF(mmad_vib_reparam_fwd(dt, B, h->btl, 1, s.out, a.Np, nullptr, nullptr, 0, 0, 1, w.zbuf,
-                                  h->L[h->n_enc].Kp, nullptr, st));
-    }
-  }
-  // pass 2: x_hat through the encoder, diff against pass-1 activations
-  const void* cur = w.l[nL - 1].out;
-  int coff = h->L[0].K;
-  for (int e = 0; e < h->n_enc; ++e) {
-    const AeLayer& a = h->L[e];
-    LayerWS& s = w.l[e];
-    GemmEpi ep = fwd_epi(h, w, a, s, B, s.dy, false);
-    if (a.bn) {
-      ep.bn_scale = s.scale;
-      ep.bn_shift = s.shift;
-    }
-    ep.ref = x3 ? (const void*)s.ref32 : (a.bn ? s.y : s.out);
-    ep.ldref = a.Np;
-    ep.rowsq = s.rowsq;
-    ep.ldrow = w.Mpe;
-    ep.diff = diffs ? diffs + coff : nullptr;
-    ep.lddiff = ld_diff;
-    nap_route(ep, e + 1);
-    const void* wt = weights_dt(h, a, dt, ep);
-    RET_IF(ae_gemm(h, w, dt, GEMM_EPI_SCORE, cur, a.Kp, wt, a.Kp, w.Mpe, a.Np, a.Kp, ep, st));
-    coff += a.N;
-    cur = s.dy;
-  }
-  // per-window sums: layer_sq[0] from the decoder's last layer, [1+e] from pass 2
-  MmadReduceJobs jobs{};
-  const AeLayer& last = h->L[nL - 1];
-  jobs.j[0] = MmadReduceJob{w.l[nL - 1].rowsq, layer_sq, last.Np / 128, w.Mpd, B, B, 1.f, 0,
-                            nullptr, 0, 0.f};
-  for (int e = 0; e < h->n_enc; ++e)
-    jobs.j[e + 1] = MmadReduceJob{w.l[e].rowsq, layer_sq + (size_t)(e + 1) * ld_sq,
-                                  h->L[e].Np / 128, w.Mpe, B, B, 1.f, 0, nullptr, 0, 0.f};
-  MMAD_CHECK_ARG(h->n_enc + 1 <= MMAD_MAX_REDUCE_JOBS, "too many encoder layers");
-  RET_IF(mmad_reduce_jobs(jobs, h->n_enc + 1, B, st));
-  if (!nap) return MMAD_OK;
-  // the NAP run as mmad_nap_score forms it: one SCORE GEMM (no reference, bias
-  // after the product, colw = w) and the column sum of its row partials
-  GemmEpi ep{};
-  ep.M = B; ep.N = nf.R; ep.out = nullptr; ep.ldo = nf.Rp; ep.bias = nf.bias; ep.act = MMAD_ACT_NONE;
-  ep.ref = nullptr; ep.ldref = nf.Rp; ep.rowsq = w.nap_rowsq; ep.ldrow = w.Mpe; ep.colw = nf.w;
-  const void* vt = nap_x3 ? (const void*)nf.vt_planes : (const void*)nf.vt;
-  RET_IF(ae_gemm(h, w, nf.dtype, GEMM_EPI_SCORE, w.nap_x, nf.Kp, vt, nf.Kp, w.Mpe, nf.Rp, nf.Kp, ep, st));
-  // (N = Np = B: nothing past nap[B) is written -- the next batch's scores, or the caller's memory)
-  return mmad_colsum(nf.Rp / 128, B, B, w.nap_rowsq, w.Mpe, 1.f / (float)nf.R, nap, st);
-}
-
-// a NAP-writing entry point's preconditions (nothing is launched on failure)
-static int check_nap(const mmad_ae* h, const float* nap, const char* who) {
-  MMAD_CHECK_ARG(nap, "%s: null nap output", who);
-  MMAD_CHECK_ARG(h->nap.on, "%s: no NAP fit attached (mmad_ae_set_nap)", who);
-  MMAD_CHECK_ARG(h->nap.dtype != MMAD_BF16X3 || score_dt(h) == MMAD_BF16X3,
-                 "%s: the attached fit's MMAD_BF16X3 NAP GEMM needs the score planes it was attached with", who);
-  return MMAD_OK;
-}
-
-int mmad_ae_score_nap(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq, float* nap,
-                      void* ws, int64_t ws_bytes, void* stream) {
-  MMAD_CHECK_ARG(h && h->params && h->running, "ae_score_nap: unbound handle");
-  MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && layer_sq, "ae_score_nap: bad args");
-  RET_IF(check_nap(h, nap, "ae_score_nap"));
-  AeWS w;
-  carve(h, B >= 1 ? B : 1, 1, nullptr, w);
-  MMAD_CHECK_ARG(B >= 1 && ws && ws_bytes >= w.bytes, "ae_score_nap: bad batch or workspace too small");
-  RET_IF(refresh_planes(h, (hipStream_t)stream));
-  RET_IF(prepare_ws(h, B, 1, ws, ws_bytes, w, (hipStream_t)stream));
-  return score_batch(h, x, ld_x, B, layer_sq, B, nullptr, w, (hipStream_t)stream, nap);
-}
-
-int mmad_ae_score(mmad_ae* h, const float* x, int ld_x, int B, float* layer_sq, float* diffs,
-                  void* ws, int64_t ws_bytes, void* stream) {
-  MMAD_CHECK_ARG(h && h->params && h->running, "ae_score: unbound handle");
-  MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && layer_sq, "ae_score: bad args");
-  RET_IF(refresh_planes(h, (hipStream_t)stream));
-  AeWS w;
-  RET_IF(prepare_ws(h, B, 1, ws, ws_bytes, w, (hipStream_t)stream));
-  return score_batch(h, x, ld_x, B, layer_sq, B, diffs, w, (hipStream_t)stream);
-}
-
-// base of the weight operand the score GEMMs read (a captured pass's key)
-static const void* score_weights(const mmad_ae* h) {
-  return h->planes ? (const void*)h->planes : weights(h, h->L[0]);
-}
-
-// the whole N-window pass, batch by batch, on stream st
-static int score_pass(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch, float* layer_sq,
-                      int64_t ld_sq, float* nap, void* ws, int64_t ws_bytes, hipStream_t st) {
-  for (int64_t s0 = 0; s0 < N; s0 += batch) {
-    const int B = (int)std::min<int64_t>(batch, N - s0);
-    AeWS w;
-    RET_IF(prepare_ws(h, B, 1, ws, ws_bytes, w, st));
-    RET_IF(score_batch(h, x + s0 * ld_x, ld_x, B, layer_sq + s0, ld_sq, nullptr, w, st,
-                       nap ? nap + s0 : nullptr));
-  }
-  return MMAD_OK;
-}
-
-// the streaming pass, with the NAP output (nullable: the pass without NAP)
-static int score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch, float* layer_sq,
-                        int64_t ld_sq, float* nap, void* ws, int64_t ws_bytes, int use_graph,
-                        void* stream) {
-  MMAD_CHECK_ARG(h && h->params && h->running, "ae_score_stream: unbound handle");
-  MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && layer_sq && N >= 1 && batch >= 1 && ld_sq >= N,
-                 "ae_score_stream: bad args (N=%lld batch=%d ld_sq=%lld)", (long long)N, batch,
-                 (long long)ld_sq);
-  hipStream_t st = (hipStream_t)stream;
-  // stale score planes are re-split here, on the caller's stream and outside
-  // the captured pass: a replay reads whatever the planes hold when it runs
-  RET_IF(refresh_planes(h, st));
-  const void* nap_vt = nap ? (const void*)h->nap.vt : nullptr;
-  if (!use_graph) return score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, st);
-  for (auto& g : h->graphs) {
-    if (g.x == x && g.ld_x == ld_x && g.N == N && g.batch == batch && g.sq == layer_sq &&
-        g.ld_sq == ld_sq && g.ws == ws && g.wts == score_weights(h) && g.nap == nap &&
-        g.nap_vt == nap_vt) {
-      MMAD_HIP_CHECK(hipGraphLaunch(g.exec, st));
-      return MMAD_OK;
-    }
-  }
-  // first pass of this shape: run it eagerly (that also settles every GEMM
-  // tile choice, which cannot be timed under capture), then capture the same
-  // launches on the handle's capture stream for the next calls
-  RET_IF(score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, st));
-  if (!h->gstream) MMAD_HIP_CHECK(hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking));
-  hipGraph_t graph = nullptr;
-  MMAD_HIP_CHECK(hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal));
-  const int rc = score_pass(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, h->gstream);
-  const hipError_t ec = hipStreamEndCapture(h->gstream, &graph);
-  if (rc != MMAD_OK) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return rc;
-  }
-  MMAD_HIP_CHECK(ec);
-  hipGraphExec_t exec = nullptr;
-  const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  MMAD_HIP_CHECK(ei);
-  if (h->graphs.size() >= 8) {   // bounded cache: drop the oldest pass
-    (void)hipGraphExecDestroy(h->graphs.front().exec);
-    h->graphs.erase(h->graphs.begin());
-  }
-  h->graphs.push_back({x, ld_x, N, batch, layer_sq, ld_sq, ws, score_weights(h), nap, nap_vt, exec});
-  return MMAD_OK;
-}
-
-int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch,
-                         float* layer_sq, int64_t ld_sq, void* ws, int64_t ws_bytes, int use_graph,
-                         void* stream) {
-  return score_stream(h, x, ld_x, N, batch, layer_sq, ld_sq, nullptr, ws, ws_bytes, use_graph, stream);
-}
-
-int mmad_ae_score_nap_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch,
-                             float* layer_sq, int64_t ld_sq, float* nap, void* ws, int64_t ws_bytes,
-                             int use_graph, void* stream) {
-  MMAD_CHECK_ARG(h, "ae_score_nap_stream: null handle");
-  RET_IF(check_nap(h, nap, "ae_score_nap_stream"));
-  MMAD_CHECK_ARG(batch >= 1 && ws && ws_bytes >= mmad_ae_workspace_bytes(h, batch, 1),
-                 "ae_score_nap_stream: bad batch or workspace too small");
-  return score_stream(h, x, ld_x, N, batch, layer_sq, ld_sq, nap, ws, ws_bytes, use_graph, stream);
-}
-
-// ---- streaming NAP fit ------------------------------------------------------
-// the fit's part of its workspace, after the scoring workspace of `batch`
-// windows: the packed fp32 operand [Mpe][Kp] and the passes' layer sums
-struct NapFitWS {
-  int W, Kp;
-  int64_t score_bytes, x_off, sq_off, bytes;
-};
-static bool nap_fit_carve(const mmad_ae* h, int batch, int start, int end, NapFitWS& f) {
-  if (!h || batch < 1 || start < 0 || end <= start || end > h->n_enc + 1) return false;
-  f.W = diff_col(h, end) - diff_col(h, start);
-  f.Kp = mmad_roundup(f.W, MMAD_PAD);
-  const int64_t Mp = mmad_roundup(batch, MMAD_PAD);
-  f.score_bytes = mmad_ae_workspace_bytes(h, batch, 1);
-  f.x_off = (f.score_bytes + 255) / 256 * 256;
-  f.sq_off = f.x_off + Mp * f.Kp * 4;
-  f.bytes = f.sq_off + (int64_t)(h->n_enc + 1) * Mp * 4;
-  return true;
-}
-
-int64_t mmad_ae_nap_fit_workspace_bytes(const mmad_ae* h, int batch, int start, int end) {
-  NapFitWS f;
-  return nap_fit_carve(h, batch, start, end, f) ? f.bytes : -1;
-}
-
-int mmad_ae_nap_fit_stream(mmad_ae* h, int start, int end, const float* x, int ld_x, int64_t N,
-                           int batch, float* mu_r, float* v, float* mu_s, float* var,
-                           void* fit_state, int64_t fit_bytes, void* ws, int64_t ws_bytes,
-                           void* stream) {
-  MMAD_CHECK_ARG(h && h->params && h->running, "ae_nap_fit_stream: unbound handle");
-  MMAD_CHECK_ARG(start >= 0 && end > start && end <= h->n_enc + 1,
-                 "ae_nap_fit_stream: bad layer range [%d, %d) of %d diff layers", start, end, h->n_enc + 1);
-  MMAD_CHECK_ARG(N >= 2, "ae_nap_fit_stream: a fit needs N >= 2 windows (N=%lld)", (long long)N);
-  MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && batch >= 1, "ae_nap_fit_stream: bad input or batch");
-  MMAD_CHECK_ARG(mu_r && v && mu_s && var, "ae_nap_fit_stream: null output");
-  NapFitWS f;
-  nap_fit_carve(h, batch, start, end, f);
-  MMAD_CHECK_ARG(ws && ws_bytes >= f.bytes, "ae_nap_fit_stream: workspace too small (%lld < %lld bytes)",
-                 (long long)ws_bytes, (long long)f.bytes);
-  MMAD_CHECK_ARG(((uintptr_t)ws) % 256 == 0, "ae_nap_fit_stream: workspace must be 256-byte aligned");
-  const int64_t need = mmad_nap_fit_state_bytes(f.W);
-  MMAD_CHECK_ARG(fit_state && need > 0 && fit_bytes >= need && ((uintptr_t)fit_state) % 256 == 0,
-                 "ae_nap_fit_stream: fit state too small or unaligned (%lld < %lld bytes)",
-                 (long long)fit_bytes, (long long)need);
-  hipStream_t st = (hipStream_t)stream;
-  float* op = (float*)((char*)ws + f.x_off);
-  float* sq = (float*)((char*)ws + f.sq_off);
-  const DiffSink sink{start, end, f.W, f.Kp, false, op};
-  RET_IF(refresh_planes(h, st));
-  RET_IF(mmad_nap_fit_begin(f.W, fit_state, fit_bytes, stream));
-  for (int pass = 0; pass < 3; ++pass) {
-    for (int64_t s0 = 0; s0 < N; s0 += batch) {
-      const int B = (int)std::min<int64_t>(batch, N - s0);
-      AeWS w;
-      RET_IF(prepare_ws(h, B, 1, ws, f.score_bytes, w, st));
-      RET_IF(score_batch(h, x + s0 * ld_x, ld_x, B, sq, w.Mpe, nullptr, w, st, nullptr, &sink));
-      if (pass == 0)
-        RET_IF(mmad_nap_fit_accumulate_sums(f.W, B, op, f.Kp, fit_state, fit_bytes, stream));
-      else if (pass == 1)
-        RET_IF(mmad_nap_fit_accumulate_gram(f.W, B, op, f.Kp, mu_r, fit_state, fit_bytes, stream));
-      else
-        RET_IF(mmad_nap_fit_accumulate_rot(f.W, N, B, op, f.Kp, mu_r, fit_state, fit_bytes, stream));
-    }
-    if (pass == 0)
-      RET_IF(mmad_nap_fit_finish_mean(f.W, N, fit_state, fit_bytes, mu_r, stream));
-    else if (pass == 1)
-      RET_IF(mmad_nap_fit_solve(f.W, N, fit_state, fit_bytes, v, stream));
-    else
-      RET_IF(mmad_nap_fit_finish(f.W, N, fit_state, fit_bytes, mu_s, var, stream));
-  }
-  return MMAD_OK;
-}
-
 int mmad_ae_status(mmad_ae* h, void* ws, int64_t ws_bytes, void* stream) {
   MMAD_CHECK_ARG(h, "ae_status: null handle");
   // no split-K GEMM / fused-BN barrier can have run unless the dtype /
@@ -2249,202 +1540,8 @@ int mmad_ae_graph_count(const mmad_ae* h) {
 
 int mmad_ae_clear_graphs(mmad_ae* h) {
   MMAD_CHECK_ARG(h, "ae_clear_graphs: null handle");
-  for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
   h->graphs.clear();
-  for (auto& g : h->ographs) (void)hipGraphExecDestroy(g.exec);
   h->ographs.clear();
   h->online_ready = nullptr;   // a new fit: another operand width
-  return MMAD_OK;
-}
-
-// ---- online scoring: B <= 16 windows through the 16-row weight stream -------
-// (mmad_skinny.hip).  The batch path above pads such a call to 128 rows and
-// spends its ~30 launches on zeros; here every layer is one launch that reads
-// its weights once.  All buffers live in a caller-owned state, carved below.
-struct OnlineWS {
-  void* xin = nullptr;             // packed input [16][Kp0]
-  std::vector<void*> y, p2;        // pass-1 outputs per layer; pass-2 outputs per encoder layer
-  void* zbuf = nullptr;            // VIB: z [128][Kp] as mmad_vib_reparam_fwd writes it
-  float *scale = nullptr, *shift = nullptr;   // folded eval-BN constants [n_bn]
-  std::vector<float*> rs;          // row partials per diff layer [Np/16][16]
-  float* nap_x = nullptr;          // packed NAP operand [16][nap.Kp] (fp32)
-  float* nap_rs = nullptr;         // the NAP launch's row partials [Rp/16][16]
-  int64_t bytes = 0;
-};
-
-static void online_carve(const mmad_ae* h, char* base, OnlineWS& o) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) -> char* {
-    off = (off + 255) / 256 * 256;
-    char* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  };
-  const int64_t E = (int64_t)esz(h->dtype);
-  const int nL = (int)h->L.size();
-  o.xin = take(16 * h->L[0].Kp * E);
-  o.y.resize(nL);
-  for (int l = 0; l < nL; ++l) o.y[l] = take(16 * h->L[l].Np * E);
-  if (h->vib) o.zbuf = take((int64_t)MMAD_PAD * h->L[h->n_enc].Kp * E);
-  o.p2.resize(h->n_enc);
-  for (int e = 0; e < h->n_enc; ++e) o.p2[e] = take(16 * h->L[e].Np * E);
-  o.scale = (float*)take(std::max<int64_t>(h->n_bn, 1) * 4);
-  o.shift = (float*)take(std::max<int64_t>(h->n_bn, 1) * 4);
-  o.rs.resize(h->n_enc + 1);
-  o.rs[0] = (float*)take((int64_t)h->L[nL - 1].Np * 4);   // [Np/16][16]
-  for (int e = 0; e < h->n_enc; ++e) o.rs[e + 1] = (float*)take((int64_t)h->L[e].Np * 4);
-  if (h->nap.on) {
-    o.nap_x = (float*)take(16 * (int64_t)h->nap.Kp * 4);
-    o.nap_rs = (float*)take((int64_t)h->nap.Rp * 4);
-  }
-  o.bytes = (off + 255) / 256 * 256;
-}
-
-int64_t mmad_ae_online_state_bytes(const mmad_ae* h) {
-  if (!h) return -1;
-  OnlineWS o;
-  online_carve(h, nullptr, o);
-  return o.bytes;
-}
-
-// the launches of one pass on stream st (eager, or into a capture)
-static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int s1, const float* thr,
-                       float* out, uint8_t* flags, const OnlineWS& o, hipStream_t st) {
-  const int dt = h->dtype;
-  const int nL = (int)h->L.size();
-  const mmad_ae::NapFit& nf = h->nap;
-  RET_IF(mmad_pack_input(dt, B, h->L[0].K, 16, h->L[0].Kp, x, ld_x, o.xin, st));
-  MmadOnlineFold f{};
-  f.n_bn = (int)h->n_bn;
-  for (const AeLayer& a : h->L)
-    if (a.bn) {
-      f.bn_off[f.n] = (int)a.bn_off; f.N[f.n] = a.N; f.g_off[f.n] = a.g_off; f.be_off[f.n] = a.be_off;
-      ++f.n;
-    }
-  RET_IF(mmad_online_fold(f, h->params, h->running, h->bn_eps, o.scale, o.shift, st));
-  // diff layer j's diffs into the NAP operand (columns relative to the range's first)
-  auto route = [&](MmadSkinny& a, int j) {
-    if (!nf.on || j < nf.start || j >= nf.end) return;
-    a.diff = o.nap_x + (diff_col(h, j) - diff_col(h, nf.start));
-    a.lddiff = nf.Kp;
-  };
-  auto layer = [&](const AeLayer& L, const void* in, void* y) {
-    MmadSkinny a{};
-    a.M = B; a.N = L.N; a.Np = L.Np; a.Kp = L.Kp;
-    a.x = in; a.w = weights(h, L); a.bias = h->params + L.b_off; a.act = L.act; a.slope = h->slope;
-    if (L.bn) { a.scale = o.scale + L.bn_off; a.shift = o.shift + L.bn_off; }
-    a.y = y;
-    return a;
-  };
-  // pass 1: eval forward; the decoder's last layer scores d0 = x_hat - x
-  for (int l = 0; l < nL; ++l) {
-    const AeLayer& L = h->L[l];
-    const void* in = l == 0 ? o.xin : (h->vib && l == h->n_enc ? o.zbuf : o.y[l - 1]);
-    MmadSkinny a = layer(L, in, o.y[l]);
-    if (l == nL - 1) {
-      a.ref = o.xin; a.ref_f32 = 0; a.ldref = h->L[0].Kp;
-      a.rowsq = o.rs[0];
-      route(a, 0);
-    }
-    RET_IF(mmad_skinny_launch(dt, a, st));
-    if (h->vib && l == h->n_enc - 1)
-      RET_IF(mmad_vib_reparam_fwd(dt, B, h->btl, 1, o.y[l], L.Np, nullptr, nullptr, 0, 0, 1, o.zbuf,
-                                  h->L[h->n_enc].Kp, nullptr, st));
-  }
-  // pass 2: x_hat through the encoder, each layer against its pass-1 output
-  const void* cur = o.y[nL - 1];
-  for (int e = 0; e < h->n_enc; ++e) {
-    const AeLayer& L = h->L[e];
-    MmadSkinny a = layer(L, cur, o.p2[e]);
-    a.ref = o.y[e]; a.ref_f32 = 0; a.ldref = L.Np;
-    a.rowsq = o.rs[e + 1];
-    route(a, e + 1);
-    RET_IF(mmad_skinny_launch(dt, a, st));
-    cur = o.p2[e];
-  }
-  // the NAP run: the same kernel on the fit's fp32 V^T (K = W, N = R), bias
-  // after the product, colw = 1 / var, no reference
-  if (nf.on) {
-    MmadSkinny a{};
-    a.M = B; a.N = nf.R; a.Np = nf.Rp; a.Kp = nf.Kp;
-    a.x = o.nap_x; a.w = nf.vt; a.bias = nf.bias; a.act = MMAD_ACT_NONE;
-    a.colw = nf.w; a.rowsq = o.nap_rs;
-    RET_IF(mmad_skinny_launch(MMAD_F32, a, st));
-  }
-  MmadOnlineFinish fin{};
-  fin.B = B; fin.n_diff = h->n_enc + 1;
-  fin.rs[0] = o.rs[0]; fin.tiles[0] = h->L[nL - 1].Np / 16; fin.widths[0] = h->L[0].K;
-  for (int e = 0; e < h->n_enc; ++e) {
-    fin.rs[e + 1] = o.rs[e + 1]; fin.tiles[e + 1] = h->L[e].Np / 16; fin.widths[e + 1] = h->L[e].N;
-  }
-  fin.sap_start = s0; fin.sap_end = s1;
-  if (nf.on) { fin.nap_rs = o.nap_rs; fin.nap_tiles = nf.Rp / 16; fin.nap_scale = 1.f / (float)nf.R; }
-  fin.out = out; fin.flags = flags; fin.thresholds = thr;
-  return mmad_online_finish(fin, st);
-}
-
-int mmad_ae_online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
-                         const float* thresholds, float* out, uint8_t* flags, void* state,
-                         int64_t state_bytes, int use_graph, void* stream) {
-  MMAD_CHECK_ARG(h, "ae_online_score: null handle");
-  MMAD_CHECK_ARG(B >= 1 && B <= 16, "ae_online_score: B=%d outside 1..16 (the batch path, "
-                 "mmad_ae_score_stream, serves larger calls)", B);
-  const int64_t need = mmad_ae_online_state_bytes(h);
-  MMAD_CHECK_ARG(state && state_bytes >= need, "ae_online_score: online state null or too small "
-                 "(%lld < %lld bytes, mmad_ae_online_state_bytes)", (long long)(state ? state_bytes : 0),
-                 (long long)need);
-  MMAD_CHECK_ARG(((uintptr_t)state) % 256 == 0, "ae_online_score: state must be 256-byte aligned");
-  MMAD_CHECK_ARG(h->params && h->running, "ae_online_score: unbound handle");
-  MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && out, "ae_online_score: bad args (null x / out, ld_x=%d)", ld_x);
-  MMAD_CHECK_ARG(score_dt(h) != MMAD_BF16X3, "ae_online_score: score planes attached "
-                 "(MMAD_BF16X3): split-bf16 planes are not supported on the online path");
-  MMAD_CHECK_ARG(!h->nap.on || h->nap.dtype == MMAD_F32, "ae_online_score: the attached fit's NAP "
-                 "GEMM is MMAD_BF16X3: not supported on the online path (attach an MMAD_F32 fit)");
-  const int nd = h->n_enc + 1;
-  MMAD_CHECK_ARG(nd <= MMAD_ONLINE_MAX_DIFF && (int)h->L.size() <= MMAD_ONLINE_MAX_LAYERS,
-                 "ae_online_score: too many layers");
-  // the reference's clamping (utils/metric.py:155-171)
-  int s0 = sap_start < 0 ? 0 : sap_start, s1 = sap_end;
-  if (s0 > nd - 1) s0 = nd - 1;
-  if (s1 - s0 < 1) s1 = s0 + 1;
-  if (s1 > nd) s1 = nd;
-  hipStream_t st = (hipStream_t)stream;
-  OnlineWS o;
-  online_carve(h, (char*)state, o);
-  if (h->nap.on && h->online_ready != state) {
-    MMAD_HIP_CHECK(hipMemsetAsync(o.nap_x, 0, 16 * (size_t)h->nap.Kp * 4, st));
-    h->online_ready = state;
-  }
-  if (!use_graph) return online_pass(h, x, ld_x, B, s0, s1, thresholds, out, flags, o, st);
-  const void* wts = weights(h, h->L[0]);
-  const void* nap_vt = h->nap.on ? (const void*)h->nap.vt : nullptr;
-  for (auto& g : h->ographs) {
-    if (g.x == x && g.ld_x == ld_x && g.B == B && g.sap_start == s0 && g.sap_end == s1 &&
-        g.thr == thresholds && g.out == out && g.flags == flags && g.state == state && g.wts == wts &&
-        g.nap_vt == nap_vt) {
-      MMAD_HIP_CHECK(hipGraphLaunch(g.exec, st));
-      return MMAD_OK;
-    }
-  }
-  RET_IF(online_pass(h, x, ld_x, B, s0, s1, thresholds, out, flags, o, st));
-  if (!h->gstream) MMAD_HIP_CHECK(hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking));
-  hipGraph_t graph = nullptr;
-  MMAD_HIP_CHECK(hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal));
-  const int rc = online_pass(h, x, ld_x, B, s0, s1, thresholds, out, flags, o, h->gstream);
-  const hipError_t ec = hipStreamEndCapture(h->gstream, &graph);
-  if (rc != MMAD_OK) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return rc;
-  }
-  MMAD_HIP_CHECK(ec);
-  hipGraphExec_t exec = nullptr;
-  const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  MMAD_HIP_CHECK(ei);
-  if (h->ographs.size() >= 8) {   // bounded cache: drop the oldest pass
-    (void)hipGraphExecDestroy(h->ographs.front().exec);
-    h->ographs.erase(h->ographs.begin());
-  }
-  h->ographs.push_back({x, ld_x, B, s0, s1, thresholds, out, flags, state, wts, nap_vt, exec});
   return MMAD_OK;
 }

@@ -1,0 +1,438 @@
+// Internal (non-ABI) state of the whole-autoencoder executor: the handle, the
+// workspace carve and the helpers shared by mmad_ae.hip (lifecycle, workspace,
+// training executor), mmad_ae_score.hip (batch / streaming score path, NAP
+// fit) and mmad_ae_online.hip (16-row online path), plus the one
+// capture-and-replay cache behind their hipGraph paths.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "mmad_common.h"
+#include "mmad_gemm.h"
+#include "mmad_ops.h"
+#include "mmad_comm.h"
+
+#define RET_IF(x)                    \
+  do {                               \
+    int r_ = (x);                    \
+    if (r_ != MMAD_OK) return r_;    \
+  } while (0)
+
+namespace mmad_ae_impl {
+
+struct AeLayer {
+  int K, N, Kp, Np;
+  int act, bn, enc;
+  int64_t w_off, b_off, g_off, be_off, bn_off;
+};
+
+// Bounded cache of instantiated hipGraphs, oldest first.  Key: a plain struct
+// with operator== holding everything a captured pass bakes in (its call
+// signature).  A hit is a linear scan over at most `cap` keys, no allocation.
+template <class Key>
+class GraphCache {
+ public:
+  explicit GraphCache(size_t cap) : cap_(cap) {}
+  GraphCache(const GraphCache&) = delete;
+  GraphCache& operator=(const GraphCache&) = delete;
+  ~GraphCache() { clear(); }
+  hipGraphExec_t find(const Key& key) const {
+    for (const Entry& e : entries_)
+      if (e.key == key) return e.exec;
+    return nullptr;
+  }
+  // takes ownership of exec; a full cache drops its oldest entry
+  void insert(const Key& key, hipGraphExec_t exec) {
+    if (entries_.size() >= cap_) {
+      (void)hipGraphExecDestroy(entries_.front().exec);
+      entries_.erase(entries_.begin());
+    }
+    entries_.push_back(Entry{key, exec});
+  }
+  void clear() {
+    for (Entry& e : entries_) (void)hipGraphExecDestroy(e.exec);
+    entries_.clear();
+  }
+  size_t size() const { return entries_.size(); }
+
+ private:
+  struct Entry { Key key; hipGraphExec_t exec; };
+  std::vector<Entry> entries_;
+  size_t cap_;
+};
+
+// the key of a captured mmad_ae_score_stream pass: one graph per (input,
+// output, workspace, N, batch)
+struct ScoreKey {
+  const float* x; int64_t ld_x, N; int batch; float* sq; int64_t ld_sq; void* ws;
+  const void* wts;   // weight operand base (the bf16 shadow may be re-pointed)
+  float* nap;        // NAP output (null: a pass without it) and the fit it was captured with
+  const void* nap_vt;
+  bool operator==(const ScoreKey& o) const {
+    return x == o.x && ld_x == o.ld_x && N == o.N && batch == o.batch && sq == o.sq &&
+           ld_sq == o.ld_sq && ws == o.ws && wts == o.wts && nap == o.nap && nap_vt == o.nap_vt;
+  }
+};
+// ... of a captured 16-row mmad_ae_online_score pass
+struct OnlineKey {
+  const float* x; int ld_x, B, sap_start, sap_end; const float* thr; float* out; uint8_t* flags;
+  void* state; const void* wts; const void* nap_vt;
+  bool operator==(const OnlineKey& o) const {
+    return x == o.x && ld_x == o.ld_x && B == o.B && sap_start == o.sap_start && sap_end == o.sap_end &&
+           thr == o.thr && out == o.out && flags == o.flags && state == o.state && wts == o.wts &&
+           nap_vt == o.nap_vt;
+  }
+};
+// ... of a captured fused train step (mmad_ae_train_step_graph)
+struct TrainKey {
+  int B, k, ld_x, xvec, has_eps, dw_main, ev_every, keep_grads;
+  const void* ws;
+  const void* shadow;   // the bf16 shadow the captured kernels read / write
+  float beta_kl, b1, b2, aeps;
+  bool operator==(const TrainKey& o) const {
+    return B == o.B && k == o.k && ld_x == o.ld_x && xvec == o.xvec && has_eps == o.has_eps &&
+           ws == o.ws && shadow == o.shadow && dw_main == o.dw_main && ev_every == o.ev_every &&
+           keep_grads == o.keep_grads && beta_kl == o.beta_kl && b1 == o.b1 && b2 == o.b2 &&
+           aeps == o.aeps;
+  }
+};
+
+}  // namespace mmad_ae_impl
+
+struct mmad_ae {
+  int dtype, n_enc, n_dec, vib, btl;
+  float slope, bn_eps, bn_mom;
+  std::vector<mmad_ae_impl::AeLayer> L;
+  int64_t n_params, n_weight, n_bn;
+  float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *running = nullptr;
+  void* shadow = nullptr;
+  // bf16 ping-pong: the fused step's Adam writes the new weights into
+  // shadow_alt while this step's backward still reads shadow, then the two
+  // swap; so a dW GEMM need not wait for its layer's bwd-data GEMM
+  void* shadow_alt = nullptr;
+  // split-bf16 scoring (mmad_ae_set_score_planes, F32 handles): bf16
+  // [2][n_weight] weight planes; the eval forward / score GEMMs then run as
+  // MMAD_BF16X3.  planes_stale: the fp32 weights were (or may have been)
+  // written since the last split; the scoring entry points re-split first
+  void* planes = nullptr;
+  bool planes_stale = true;
+  // streamed NAP (mmad_ae_set_nap): the fit of the concatenated diffs of the
+  // diff layers [start, end) (0 = x_hat - x, 1 + e = encoder layer e), all
+  // caller-owned.  dtype: the NAP GEMM's (MMAD_F32: fp32 operand written
+  // through the score GEMMs' diff output; MMAD_BF16X3: plane operand written
+  // through their diff-plane output, vt split into vt_planes at attach)
+  struct NapFit {
+    bool on = false;
+    int start = 0, end = 0, K = 0, Kp = 0, R = 0, Rp = 0, dtype = MMAD_F32;
+    const float *vt = nullptr, *bias = nullptr, *w = nullptr;
+    void* vt_planes = nullptr;
+  } nap;
+  // side stream + events for the dW / Adam overlap (created at bind time)
+  hipStream_t side = nullptr;
+  std::vector<hipEvent_t> ev_fork, ev_data;
+  hipEvent_t ev_join = nullptr;
+  hipEvent_t ev_loss = nullptr;   // fused step: forward done -> the loss reduction on the side stream
+  // the schedule, copied from the tune table at create (include/mmad.h knobs
+  // 16-27): one schedule per handle, whatever the table says later
+  unsigned ev_flags_ = 0;
+  int loss_side = 1;      // knob 23: reduce the loss on the side stream after the forward
+  int side_prio_hi = 0;   // knob 26
+  // knob 15: > 0 = the side stream is created behind a CU mask that leaves
+  // this many CUs (evenly spaced over the mask) to the main stream alone
+  int side_cu_held = 0;
+  // data-parallel step: the small bucket (bias / gamma / beta grads + loss)
+  // goes on the comm stream right after the bwd-data GEMM of this layer
+  // (ahead of this layer's and the lower layers' weight buckets); knob 24
+  int dp_small_at = 1;
+  // data-parallel step: sharded weight buckets (knob 28); master_stale: the
+  // bf16 model's fp32 master weights / every model's Adam moments are
+  // current only on their owning rank since the last mmad_ae_dp_sync_master
+  int dp_shard = 1;
+  // data-parallel step: consecutive layers' weight gradients (backward
+  // order) share one exchange bucket until it holds at least dp_bucket_mib
+  // MiB of fp32 gradient (knob 30; 0 = one bucket per layer)
+  int dp_bucket_mib = 8;
+  // data-parallel step: from this many padded rows each side-stream dW GEMM
+  // is issued as soon as its own dz is complete instead of with its bucket's
+  // closing layer (knob 14; 0 = one fork per bucket)
+  int dp_fork_rows = 1024;
+  bool master_stale = false;
+  int mse_tiles = 0;   // loss partials written by the last MSE GEMM
+  // data parallelism: RCCL communicator (not owned), its stream and events
+  mmad_comm* comm = nullptr;
+  hipStream_t cstream = nullptr;
+  std::vector<hipEvent_t> ev_dw;
+  // torch-exchange data parallelism (mmad_ae_dw_events): the forward+backward
+  // without Adam records ev_xdw[l] after dW_l and ev_xdata[l] after bwd-data of
+  // l.  System-scope fences (unlike the executor's own events): the exchange
+  // may read the gradients with a copy engine, which does not see the L2
+  bool dw_events = false;
+  std::vector<hipEvent_t> ev_xdw, ev_xdata;
+  // optional bf16 gradient exchange (mmad_ae_set_grad_bf16): n_weight bf16
+  void* grad_bf16 = nullptr;
+  hipEvent_t ev_small = nullptr, ev_cdone = nullptr;
+  // schedule study (knob 29): every side-stream dW + Adam GEMM held until the
+  // main stream has enqueued the whole bwd-data chain (ev_hold), to separate
+  // the chain's in-step contention from its barrier costs
+  int side_hold = 0;
+  // knob 33 (ping-pong steps): the side-stream dW + Adam GEMMs of the top
+  // dw_late layers fork behind the layer's bwd-data + BN apply instead of at
+  // its dz, so the largest dW does not share the CUs with the apply below it
+  int dw_late = 0;
+  // knob 34 (ping-pong steps): each side-stream dW's fork event (dz_l ready)
+  // completed by the launch that produces dz_l (the BN-backward apply or the
+  // bwd-data GEMM: hipExtLaunchKernel stop event) instead of a marker packet
+  // recorded on the main stream before the bwd-data GEMM of l -- each marker
+  // held the main stream's next dispatch ~5 us; the top layer's fork is the
+  // loss reduction's wait on the MSE launch, already on the side stream
+  int fork_on_kernel = 1;
+  // knob 35 (ping-pong steps): from this layer down, side-stream dW GEMMs
+  // fork in pairs -- every other layer's dz gets no fork event and its dW is
+  // issued with the next lower layer's (where the side stream lags the chain
+  // by more than a layer anyway, each fork saved is a ~5-us hold on the
+  // main stream; 0 = every layer forks)
+  int fork_pair_below = 0;
+  // ping-pong steps (mmad_ae_set_dw_group): consecutive side-stream layers
+  // whose dW + Adam GEMM takes the 64x64 tile are issued as ONE grouped launch
+  // (mmad_gemm_dispatch_group) at the lowest member's fork -- at 4096 rows
+  // each of the narrow layers' launches is one block's 64-stage K loop,
+  // 23-25 us for 16 to 135 blocks, and they ran back to back.  blocks = the
+  // group's budget of padded blocks (0 = off: every dW its own launch; < 0 =
+  // one resident round of the kernel), members = at most this many per group
+  int dw_group_blocks = MMAD_DW_GROUP_BLOCKS_DEFAULT;
+  int dw_group_members = MMAD_GEMM_GROUP_MAX;
+  hipEvent_t ev_hold = nullptr;
+  // fused step: dW GEMMs of layers < dw_main run on the caller's stream
+  // (knob 19; tools/sched_sweep.py: 0.499 ms (2) vs 0.512 (1) vs 0.523 (3));
+  // keep_grads (knob 25): also write dW to the grads buffer
+  int dw_main = 2;
+  // ping-pong schedule per call from this many padded rows (bf16 with a
+  // shadow pair; knob 20), with dw_main_ping main-stream dW GEMMs (knob 21):
+  // VIB B=4096 0.941-0.945 vs 0.995-0.999 ms/step, B=1024 0.450-0.455 vs
+  // 0.442-0.449 (profiles/r02bu_*, r02bv_*)
+  int pair_rows = 4096;
+  int dw_main_ping = 1;
+  int keep_grads = 0;
+  // train-mode BN: fold the batch statistics into the consumer's weights
+  // (bn_fold_k; the bf16 throughput path) or normalise the activations into y
+  // (bn_train_apply_k; the exact-fp32 parity path: folding contracts the raw,
+  // un-centred activations and cancels the mean back out, which costs the
+  // fp32 path ~10x the reference's rounding error on BN-producer layers).
+  // Set at create from the dtype and knob 16.
+  int fold = 1;
+  // train-mode BN inside the producing GEMM (bn_mode 2, MMAD_BN_MODE): the
+  // forward GEMM's epilogue finishes the batch statistics and writes y, the
+  // bwd-data GEMM's epilogue writes dz (a per-column-tile barrier between the
+  // blocks of one column, mmad_gemm_mfma.hip) -- no finalize / fold / apply
+  // launches.  Layers whose grid cannot be co-resident fall back to mode 0
+  // (apply kernels).  0 = apply kernels, 1 = fold, 2 = fused (knob 16).  Default: bf16
+  // 2 up to bn_fused_rows padded rows per call (measured: D=2048 B=1024
+  // 0.495 ms/step fused vs 0.531 apply vs 0.536 fold; B=4096 VIB 1.33 fused
+  // vs 1.32 apply vs 1.27 fold -- more tiles per column, longer barrier
+  // waits), fold above; fp32 0 (the parity path).
+  int bn_mode = 0;
+  // backward BN schedule override for the bf16 path (knob 17: -1 =
+  // the forward's; 2 = fused into the bwd-data GEMMs whatever the forward did:
+  // the fused backward needs only a, the saved mean / rstd and gamma, which
+  // every forward schedule leaves)
+  int bn_mode_bwd = -1;
+  int bn_fused_rows = 2048;   // knob 18
+  // fused step: record the "bwd-data of l done" event only every ev_every-th
+  // side-stream layer (each record costs a bubble on the main stream); the dW
+  // GEMMs of the layers in between wait for the next recorded one (knob 22;
+  // c2 0.435-0.440 vs 0.442-0.444 with 1, profiles/r02bv_*)
+  int ev_every = 2;
+  // the main stream's hand-off events (bwd-data -> side-stream dW, MSE ->
+  // side-stream loss) completed by the GEMM launch itself (knob 31)
+  int ev_on_kernel = 1;
+  // hipGraph cache for mmad_ae_score_stream: one captured graph per
+  // (input, output, workspace, N, batch) pass, replayed with one launch
+  mmad_ae_impl::GraphCache<mmad_ae_impl::ScoreKey> graphs{8};
+  // the same for mmad_ae_online_score: one captured 16-row pass per call
+  // signature.  online_ready: the state buffer whose NAP operand this handle
+  // has zeroed (its padding is never written again)
+  mmad_ae_impl::GraphCache<mmad_ae_impl::OnlineKey> ographs{8};
+  const void* online_ready = nullptr;
+  // kernel probe (mmad_ae_probe): timing events around ONE GEMM launch of
+  // the step, on the stream it is launched on (bench roofline, in situ)
+  mutable int probe_id = -1;
+  mutable int probe_n = 0;
+  mutable unsigned probe_mask = 0;    // layers the last probed launch covered (bit l)
+  std::vector<hipEvent_t> probe_ev;   // [2 * capacity]: start, end pairs
+  hipEvent_t probe_sync = nullptr;    // a main-stream probe's start waits for the side stream
+  // probe kinds 2 / 3: the events ride on the launch itself (hipExtLaunchKernel
+  // start / stop: the kernel's own start and end, as rocprofv3's kernel records)
+  // and nothing waits for the side stream -- the launch as it runs in the
+  // step's schedule, so the probe can stay on through a timed region
+  bool probe_kev = false;
+  // hipGraph-captured fused train steps (mmad_ae_train_step_graph): one per
+  // call signature, replayed after a host->device copy of the per-call values
+  // (a ring of pinned host slots, each reused only once its copy has run)
+  mmad_ae_impl::GraphCache<mmad_ae_impl::TrainKey> tgraphs{16};
+  static constexpr int kDynSlots = 64;
+  MmadDyn* dyn_host = nullptr;
+  hipEvent_t dyn_ev[kDynSlots] = {};
+  bool dyn_used[kDynSlots] = {};
+  int dyn_next = 0;
+  // a capture of one of the three caches' passes is open on gstream
+  // (capture_graph): no timing probe, no kernel-attached hand-off events
+  bool capturing = false;
+  bool graph_broken = false;
+  // workspace whose split-K control block this handle has zeroed
+  const void* ws_zeroed = nullptr;
+  hipStream_t gstream = nullptr;   // capture stream (the caller's may be the null stream)
+  ~mmad_ae() {
+    // the captured graphs go ahead of the stream they were captured on (the
+    // members' own destructors would run after this body)
+    tgraphs.clear();
+    for (auto e : dyn_ev)
+      if (e) (void)hipEventDestroy(e);
+    if (dyn_host) (void)hipHostFree(dyn_host);
+    for (auto e : probe_ev) (void)hipEventDestroy(e);
+    if (probe_sync) (void)hipEventDestroy(probe_sync);
+    graphs.clear();
+    ographs.clear();
+    if (gstream) (void)hipStreamDestroy(gstream);
+    for (auto e : ev_fork) (void)hipEventDestroy(e);
+    for (auto e : ev_data) (void)hipEventDestroy(e);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    if (ev_hold) (void)hipEventDestroy(ev_hold);
+    if (ev_loss) (void)hipEventDestroy(ev_loss);
+    for (auto e : ev_dw) (void)hipEventDestroy(e);
+    for (auto e : ev_xdw) (void)hipEventDestroy(e);
+    for (auto e : ev_xdata) (void)hipEventDestroy(e);
+    if (ev_small) (void)hipEventDestroy(ev_small);
+    if (ev_cdone) (void)hipEventDestroy(ev_cdone);
+    if (cstream) (void)hipStreamDestroy(cstream);
+    if (side) (void)hipStreamDestroy(side);
+  }
+};
+
+namespace mmad_ae_impl {
+
+struct LayerWS {
+  void *out, *y, *dy, *dz;
+  float *stats, *mean, *rstd, *scale, *shift, *dbpart, *rowsq;
+  float* ref32;     // x3 scoring: fp32 copy of an encoder layer's pass-1 output (else null)
+  double* bnpart;   // fp64 BN-backward column partials [Mp/64][2][Np]
+  // consumer of a train-mode BN producer: W*scale (GEMM dtype) and the
+  // per-64-column partials of sum_k shift[k] W[n][k]
+  void* wf;
+  float* cpart;
+  // this call: BN of the layer fused into its forward GEMM / into the
+  // bwd-data GEMM of the next layer (bias gradient partials per 64 rows)
+  bool fwd_fused, bwd_fused;
+  unsigned* sync_f;   // fused-BN barrier counters (MMAD_BN_SYNC_WORDS each)
+  unsigned* sync_b;
+};
+struct AeWS {
+  int B, k, Mpe, Mpd;
+  MmadDyn* dyn_dev = nullptr;    // device slot for the per-call values (graph-captured step)
+  const MmadDyn* dyn = nullptr;  // set: kernels read x / loss / noise / Adam terms from dyn_dev
+  void *xin, *zbuf, *dzin;
+  float *eps, *klpart, *misc, *lossp;
+  int64_t kl_parts;
+  // split-K workspace per stream (0 = caller's stream, 1 = side stream);
+  // the two control blocks are contiguous (one memset per call)
+  float* sk_slab[2];
+  unsigned* sk_ctl[2];
+  size_t sk_ctl_bytes;   // both split-K control blocks + the fused-BN counters
+  unsigned* bn_err;      // fused-BN barrier timeout word
+  int bn_mode;           // this call's train-mode BN schedule (0 apply, 1 fold, 2 fused)
+  int bn_mode_bwd;       // ... of the backward (2: fused into the bwd-data GEMMs; else the apply kernel)
+  // this call's fused-step schedule: ping-pong the bf16 weight shadows (the
+  // Adam of layer l writes the shadow the NEXT step reads, so dW_l waits only
+  // for dz_l) and how many of the last dW GEMMs run on the main stream
+  bool ping = false;
+  int dw_main = 2;
+  std::vector<LayerWS> l;
+  // streamed NAP (a fit attached, else null): the packed operand [Mpe][nap.Kp]
+  // (fp32, or bf16 planes [2][Mpe][nap.Kp]) and the NAP GEMM's row partials
+  void* nap_x = nullptr;
+  float* nap_rowsq = nullptr;
+  int64_t nap_x_off = -1;   // byte offset of nap_x in the workspace
+  int64_t bytes;
+};
+
+// where score_batch routes the diffs of a range of diff layers (the attached
+// fit's NAP operand, or the streaming NAP fit's own)
+struct DiffSink {
+  int start, end, K, Kp;   // diff layers [start, end), their width and its padding
+  bool x3;                 // bf16 plane operand (the attached fit's x3 NAP GEMM)
+  void* x;                 // [Mpe][Kp]
+};
+
+inline size_t esz(int dtype) { return dtype == MMAD_BF16 ? 2 : 4; }
+// dtype of the eval forward / score GEMMs
+inline int score_dt(const mmad_ae* h) { return h->planes ? MMAD_BF16X3 : h->dtype; }
+inline int rows_of(const AeWS& w, const AeLayer& a) { return a.enc ? w.B : w.B * w.k; }
+inline int prows_of(const AeWS& w, const AeLayer& a) { return a.enc ? w.Mpe : w.Mpd; }
+inline float* running_mean(const mmad_ae* h, const AeLayer& a) { return h->running + a.bn_off; }
+inline float* running_var(const mmad_ae* h, const AeLayer& a) {
+  return h->running + h->n_bn + a.bn_off;
+}
+
+// mmad_ae.hip
+void carve(const mmad_ae* h, int B, int k, char* base, AeWS& w);
+int prepare_ws(const mmad_ae* h, int B, int k, void* ws, int64_t ws_bytes, AeWS& w, hipStream_t st);
+int refresh_planes(mmad_ae* h, hipStream_t st, bool force = false);
+const void* weights(const mmad_ae* h, const AeLayer& a);
+const void* weights_dt(const mmad_ae* h, const AeLayer& a, int dt, GemmEpi& ep);
+const void* input_of(const mmad_ae* h, const AeWS& w, int l, bool train, const float** scale,
+                     const float** shift);
+GemmEpi fwd_epi(const mmad_ae* h, const AeWS& w, const AeLayer& a, const LayerWS& s, int M, void* out,
+                bool folded);
+int ae_gemm(const mmad_ae* h, const AeWS& w, int dt, int epi, const void* A, int lda, const void* B,
+            int ldb, int Mp, int Np, int K, GemmEpi ep, hipStream_t s, int* cfg = nullptr,
+            int probe = -1);
+// mmad_ae_score.hip
+int diff_col(const mmad_ae* h, int j);
+
+// Capture the launches `pass(stream)` issues into an instantiated graph: on
+// the handle's capture stream (created on first use), thread-local mode, with
+// h->capturing set for the duration.  The capture is always ended and the
+// hipGraph always destroyed.  The caller has run the same pass eagerly first
+// (that settles every GEMM tile choice, which cannot be timed under capture).
+// Returns which stage failed -- the caller owns the policy -- with the pass's
+// own code in rc (GC_PASS) or the HIP error in err (every other stage).
+enum GraphCaptureStage { GC_OK = 0, GC_BEGIN, GC_PASS, GC_END, GC_INSTANTIATE };
+struct GraphCaptureResult {
+  GraphCaptureStage stage;
+  int rc;
+  hipError_t err;
+};
+template <class Pass>
+GraphCaptureResult capture_graph(mmad_ae* h, Pass pass, hipGraphExec_t* exec) {
+  *exec = nullptr;
+  hipError_t e = h->gstream ? hipSuccess : hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal);
+  if (e != hipSuccess) return {GC_BEGIN, MMAD_OK, e};
+  h->capturing = true;
+  const int rc = pass(h->gstream);
+  h->capturing = false;
+  hipGraph_t graph = nullptr;
+  e = hipStreamEndCapture(h->gstream, &graph);
+  if (e == hipSuccess && !graph) e = hipErrorUnknown;
+  GraphCaptureResult res{GC_OK, rc, e};
+  if (rc != MMAD_OK) {
+    res.stage = GC_PASS;
+  } else if (e != hipSuccess) {
+    res.stage = GC_END;
+  } else if ((res.err = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0)) != hipSuccess) {
+    res.stage = GC_INSTANTIATE;
+  }
+  if (graph) (void)hipGraphDestroy(graph);
+  return res;
+}
+// the score / online policy: the failed stage's error is the call's (the
+// pass's own code and error string first, then the HIP error)
+inline int capture_error(const GraphCaptureResult& r) {
+  if (r.stage == GC_PASS) return r.rc;
+  MMAD_HIP_CHECK(r.err);
+  return MMAD_OK;
+}
+
+}  // namespace mmad_ae_impl

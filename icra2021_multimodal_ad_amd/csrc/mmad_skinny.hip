@@ -1,5 +1,5 @@
 // 16-row weight-streaming layer operator (mmad_fc_rows16) and the two small
-// kernels of the online scoring pass (mmad_ae_online_score, mmad_ae.hip).
+// kernels of the online scoring pass (mmad_ae_online_score, mmad_ae_online.hip).
 //
 // y[16][N] = epi(x[16][K] . W[N][K]^T) for at most 16 valid rows: the work is
 // one pass over W, so the kernel is built as a weight stream, not as a GEMM

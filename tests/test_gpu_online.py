@@ -406,6 +406,36 @@ def test_graph_replay_and_lifecycle(golden):
     sc.detach()
 
 
+def test_online_graph_cache_is_bounded_and_drops_the_oldest(golden):
+    """The online graph cache holds 8 passes.  Nine B = 10 passes that differ
+    only in the out buffer: 8 cached after the 8th and after the 9th.  The
+    first buffer again (dropped: run eagerly and captured anew) leaves 8 and
+    equals the use_graph=0 result bit for bit; the 9th buffer again leaves 8,
+    so the 9th was cached and the oldest was the one dropped."""
+    m = _model(golden)
+    nat = m._native
+    rig = _Rig(m)
+    x = torch.from_numpy(synth_windows(10, nat.enc_widths[0], seed=97)).cuda()
+    ref = rig.run(x)[0]
+    outs = [torch.full_like(rig.out, rig.canary) for _ in range(9)]
+
+    def run(o):
+        o.fill_(rig.canary)
+        nat.online_score(rig.x, 10, o, rig.state, flags=rig.flags, thresholds=rig.thr, graph=True)
+
+    assert _graphs(nat) == 0
+    for i, o in enumerate(outs):
+        run(o)
+        assert _graphs(nat) == min(i + 1, 8)
+    run(outs[0])
+    assert _graphs(nat) == 8
+    assert torch.equal(outs[0], ref)
+    run(outs[8])
+    assert _graphs(nat) == 8
+    for o in outs:
+        assert torch.equal(o, ref)
+
+
 # ------------------------------------------------------------------- 6. flags
 def test_flags_follow_the_strict_rule(fitted):
     m, _ = fitted

@@ -441,6 +441,85 @@ def test_score_stream_graph_matches_per_batch(golden, dtype):
     assert nat._lib.mmad_ae_graph_count(nat._h) == 0
 
 
+def _smoke_model(seed=11):
+    """The smoke-sized fp32 model (D = 192, bottleneck 16, 5 layers), eval mode."""
+    m, _ = _model(192, 16, 5, init_state_dict(192, 16, 5, seed=seed))
+    m.eval()
+    return m
+
+
+def test_score_graph_cache_is_bounded_and_drops_the_oldest():
+    """The score-pass graph cache holds 8 passes.  Nine passes that differ only
+    in the layer_sq buffer: 8 cached after the 8th and after the 9th.  The
+    first buffer again (dropped: run eagerly and captured anew) leaves 8 and
+    equals the use_graph=0 result bit for bit; the 9th buffer again leaves 8,
+    so the 9th was cached and the oldest was the one dropped."""
+    m = _smoke_model()
+    nat = m._native
+    count = lambda: nat._lib.mmad_ae_graph_count(nat._h)
+    x = torch.from_numpy(synth_windows(128, 192, seed=12)).cuda()
+    ref = nat.score_stream(x, 64, torch.empty((nat.n_enc + 1, 128), device="cuda"), graph=False).clone()
+    outs = [torch.full((nat.n_enc + 1, 128), float("nan"), device="cuda") for _ in range(9)]
+    assert count() == 0
+    for i, o in enumerate(outs):
+        nat.score_stream(x, 64, o, graph=True)
+        assert count() == min(i + 1, 8)
+    outs[0].fill_(float("nan"))
+    nat.score_stream(x, 64, outs[0], graph=True)
+    assert count() == 8
+    assert torch.equal(outs[0], ref)
+    outs[8].fill_(float("nan"))
+    nat.score_stream(x, 64, outs[8], graph=True)
+    assert count() == 8
+    assert torch.equal(outs[8], ref)
+    for o in outs:
+        assert torch.equal(o, ref)
+
+
+def test_score_stream_argument_error_leaves_the_graph_path_usable():
+    """mmad_ae_score_nap_stream with use_graph=1 and no fit attached returns the
+    argument error (nothing captured); an ordinary graph-mode pass on the same
+    handle then runs and is cached."""
+    from icra2021_multimodal_ad_amd import _native
+    m = _smoke_model()
+    nat = m._native
+    x = torch.from_numpy(synth_windows(128, 192, seed=12)).cuda()
+    out = torch.empty((nat.n_enc + 1, 128), device="cuda")
+    nap = torch.empty(128, device="cuda")
+    with pytest.raises(_native.NativeError, match=r"status %d: .*no NAP fit attached" % _native.MMAD_EINVAL):
+        nat.score_stream(x, 64, out, graph=True, nap_out=nap)
+    assert nat._lib.mmad_ae_graph_count(nat._h) == 0
+    ref = nat.score_stream(x, 64, torch.empty_like(out), graph=False).clone()
+    nat.score_stream(x, 64, out, graph=True)
+    assert nat._lib.mmad_ae_graph_count(nat._h) == 1
+    assert torch.equal(out, ref)
+    out.fill_(float("nan"))
+    nat.score_stream(x, 64, out, graph=True)          # the replay
+    assert nat._lib.mmad_ae_graph_count(nat._h) == 1
+    assert torch.equal(out, ref)
+
+
+def test_train_graph_cache_is_bounded():
+    """The train-step graph cache holds 16 steps.  17 graph-mode steps at B = 64
+    that differ only in beta_kl (part of the key; the plain autoencoder's
+    kernels do not read it): 16 cached, and the parameters equal, bit for bit,
+    those of a fresh handle stepped eagerly through the same 17 steps."""
+    sd = init_state_dict(192, 16, 5, seed=11)
+    x = torch.from_numpy(synth_windows(64, 192, seed=12)).cuda()
+    res = {}
+    for graph in (True, False):
+        m, _ = _model(192, 16, 5, sd)
+        m.train()
+        nat = m._native
+        nat.use_graph = graph
+        for i in range(17):
+            nat.train_step_fused(x, beta_kl=0.125 * i)
+        assert nat._lib.mmad_ae_train_graph_count(nat._h) == (16 if graph else 0)
+        res[graph] = (nat.params.clone(), nat.exp_avg.clone(), nat.exp_avg_sq.clone(), nat.running.clone())
+    for a, b in zip(res[True], res[False]):
+        assert torch.equal(a, b)
+
+
 def test_bf16_shadow_follows_load_state_dict_and_torch_optim():
     """The bf16 weight shadow must follow every write of the fp32 master made
     through the reference-shaped parameters: load_state_dict after native
