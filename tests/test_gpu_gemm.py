@@ -34,6 +34,18 @@ def _ctl_zero(ws):
     return int(ws[slab:n].view(torch.int32).abs().sum().item()) == 0
 
 
+def _bf16_close(got, want):
+    """A bf16-stored output against its float64 reference, per element:
+    |got - want| <= 2^-8 |want| + 2e-5 max|want| (round-to-nearest at 8
+    significand bits, on top of the fp32 bar; test_gpu_gemm_matrix.py)."""
+    bound = 2.0 ** -8 * want.abs() + 2e-5 * want.abs().max()
+    return bool(((got.double() - want).abs() <= bound).all())
+
+
+def _leaky(z, slope=0.2):
+    return torch.where(z > 0, z, z * float(torch.tensor(slope, dtype=torch.float32)))
+
+
 def _run(kind, dt, M, N, K, split):
     lib = _native.load()
     lib.mmad_tune_set(4, split)
@@ -209,7 +221,8 @@ def test_persistent_grid_bit_identical(kind):
     every large-row tile (256x128, 128x256, 256x256; tile 7 also issues the
     next tile's first K stages from its epilogue) forced, at a row count
     whose tiles exceed one resident round (16,384 rows: 512-1024 tiles on 256
-    CUs); outputs, BN-statistic / score-row / loss partials compared."""
+    CUs); outputs, BN-statistic / score-row / loss partials compared, and
+    each tile's ordinary-grid y held to a float64 reference at the bf16 bar."""
     lib = _native.load()
     dev = torch.device("cuda", 0)
     g = torch.Generator(device="cuda").manual_seed(5)
@@ -244,6 +257,9 @@ def test_persistent_grid_bit_identical(kind):
     # it at all (the tuned tile runs)
     epi, parts, act = {"fwd": (0, 1, 1), "fwdns": (0, 0, 1), "score": (4, 0, 1), "mse": (1, 1, 0)}[kind]
     split = lib.mmad_gemm_splitk_for(Mp, Np, Kp, BF16, epi)
+    z = x[:M, :K].double() @ w[:N, :K].double().t() + b[:N].double()
+    want_y = 2.0 * (z - tgt.double()) if kind == "mse" else _leaky(z)
+    del z
     try:
         for tile in (1, 2, 6, 7):
             want = tile if tile != 7 else {"fwd": 6, "fwdns": 7, "score": 7, "mse": -1}[kind]
@@ -251,7 +267,9 @@ def test_persistent_grid_bit_identical(kind):
             lib.mmad_tune_set(0, tile)
             lib.mmad_tune_set(12, 0)
             a = run()
-            for pk in (1, -1):                   # any nonzero value: persistent above one round
+            # the anchor of the bit-identity chain: the ordinary grid against float64
+            assert _bf16_close(a[0][:M, :N], want_y), (kind, tile)
+            for pk in (1, -1):                  # any nonzero value: persistent above one round
                 lib.mmad_tune_set(12, pk)
                 p = run()
                 torch.cuda.synchronize()
@@ -273,7 +291,8 @@ def test_register_direct_tile_bit_identical(case, N):
     256x128 / 128x... tiles fit and a forced 256x256 falls back to the tuned
     one).  The forward with
     BN-statistic partials and the sigmoid forward run CFG 6 in its place
-    (same tile, same bits)."""
+    (same tile, same bits).  The chain's anchor, tile 6's y (the NAP run: its
+    score), is held to a float64 reference at the bf16 bar."""
     lib = _native.load()
     dev = torch.device("cuda", 0)
     g = torch.Generator(device="cuda").manual_seed(11)
@@ -332,7 +351,22 @@ def test_register_direct_tile_bit_identical(case, N):
         torch.cuda.synchronize()
     finally:
         lib.mmad_tune_set(0, -1)
-    assert float(outs[6][0].float().abs().sum()) > 0
+    # the anchor of the chain (tile 6, or the tuned tile where 256 columns do
+    # not fit) against float64 of the same operands
+    z = x[:M, :K].double() @ w[:N, :K].double().t() + b[:N].double()
+    if case == "nap_colw":
+        # score[m] = (1/R) sum_j colw[j] z[m][j]^2, squared from the bf16-rounded
+        # z: each term off by at most 2 |z| 2^-8 |z|, plus the fp32 bar
+        cw = colw[:N].double()
+        want = (cw * z * z).sum(1) / N
+        bound = (cw * 2.0 ** -7 * z * z).sum(1) / N + 2e-5 * want.abs().max()
+        assert bool(((outs[6][1][:M].double() - want).abs() <= bound).all()), case
+    else:
+        a = {"fwd_relu": z.clamp_min(0.0), "fwd_none": z, "fwd_sigmoid_fallback": torch.sigmoid(z)}.get(case)
+        a = _leaky(z) if a is None else a
+        if case == "fwd_leaky_bn" or case.startswith("score"):
+            a = a * sc[:N].double() + sh[:N].double()
+        assert _bf16_close(outs[6][0][:M, :N], a), case
     for tile in (7, 8, 1, 2, 9):
         for a, b2 in zip(outs[6], outs[tile]):
             assert torch.equal(a, b2), (case, tile)
