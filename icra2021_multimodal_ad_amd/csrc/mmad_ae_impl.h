@@ -226,7 +226,7 @@ struct mmad_ae {
   // train-mode BN inside the producing GEMM (bn_mode 2, MMAD_BN_MODE): the
   // forward GEMM's epilogue finishes the batch statistics and writes y, the
   // bwd-data GEMM's epilogue writes dz (a per-column-tile barrier between the
-  // blocks of one column, mmad_gemm_mfma.hip) -- no finalize / fold / apply
+  // blocks of one column, mmad_gemm_body.h) -- no finalize / fold / apply
   // launches.  Layers whose grid cannot be co-resident fall back to mode 0
   // (apply kernels).  0 = apply kernels, 1 = fold, 2 = fused (knob 16).  Default: bf16
   // 2 up to bn_fused_rows padded rows per call (measured: D=2048 B=1024

@@ -16,7 +16,7 @@
 // the eval / score path uses).  One tile: 128x128, 512 threads (waves 2x4,
 // wave tile 64x32), K stage = 64 (128 B per row and plane): the four panels
 // A-hi, A-lo, B-hi, B-lo are 64 KB per stage, two stages in a ring.  Panels
-// use the K-major LDS image of mmad_gemm_mfma.hip (16-byte chunk j of row r
+// use the K-major LDS image of mmad_gemm_dev.h (16-byte chunk j of row r
 // stored at j ^ ((r >> 1) & 7), filled by global_load_lds, read with one
 // ds_read_b128 per fragment).  The MFMA operands are swapped (B first), so a
 // lane's accumulator quad is 4 consecutive columns of one output row and the
@@ -48,7 +48,7 @@ static_assert(X_NS * X_SLOT <= 163840, "LDS budget");
 __device__ __forceinline__ int x_swz(int r) { return (r >> 1) & 7; }
 
 // one 16-byte-per-lane LDS-DMA into the wave's 1 KiB at `dst` (wave-uniform);
-// inline asm for the reason given at dma16 in mmad_gemm_mfma.hip
+// inline asm for the reason given at dma16 in mmad_gemm_dev.h
 __device__ __forceinline__ void x_dma16(const void* src, char* dst) {
   const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(MMAD_LDS void*)dst);
   asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(lds) : "memory");
@@ -84,7 +84,7 @@ struct X3Args {
   bf16 *o_hi, *o_lo;       // output planes (nullable together)
 };
 
-// XCD-aware grouped tile order, as tile_coord in mmad_gemm_mfma.hip (S = 1)
+// XCD-aware grouped tile order, as tile_coord in mmad_gemm_dev.h (S = 1)
 __device__ __forceinline__ void x_tile(const GemmEpi& ep, int bid, int nblk, int& tm, int& tn) {
   const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
   const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);

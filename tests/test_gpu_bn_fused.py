@@ -1,7 +1,7 @@
 """Train-mode BatchNorm fused into the producing GEMMs (tune knob bn_mode = 2): the
 forward GEMM's epilogue finishes the whole-batch statistics and writes
 y = BN(a), the bwd-data GEMM's epilogue writes dz (per-column-tile barrier
-between the blocks of one output column; csrc/mmad_gemm_mfma.hip).
+between the blocks of one output column; csrc/mmad_gemm_body.h).
 
 Pinned against the reference goldens (fp32: the same bars as
 test_gpu_parity.py's train-step test -- loss rtol 1e-4, gradients within 1e-4
