@@ -43,6 +43,10 @@ SIGNATURES = {
                             _P, _P, _P]),
     "mmad_ae_online_state_bytes": (_I64, [_P]),
     "mmad_ae_online_score": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _I, _P]),
+    "mmad_fc_rows64": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _I, _I, _P, _I,
+                            _P, _P, _P]),
+    "mmad_ae_online_state_bytes64": (_I64, [_P]),
+    "mmad_ae_online_score64": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _I, _P]),
     "mmad_bn_eval_affine": (_I, [_I, _I, _P, _P, _P, _P, _F, _P, _P, _P]),
     "mmad_bn_train_apply": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P,
                                  _P]),

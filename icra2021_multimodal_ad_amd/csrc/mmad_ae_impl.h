@@ -76,14 +76,16 @@ struct ScoreKey {
            ld_sq == o.ld_sq && ws == o.ws && wts == o.wts && nap == o.nap && nap_vt == o.nap_vt;
   }
 };
-// ... of a captured 16-row mmad_ae_online_score pass
+// ... of a captured mmad_ae_online_score / mmad_ae_online_score64 pass; rows:
+// the entry point's row capacity (16 / 64: other kernels, other layouts)
 struct OnlineKey {
   const float* x; int ld_x, B, sap_start, sap_end; const float* thr; float* out; uint8_t* flags;
   void* state; const void* wts; const void* nap_vt;
+  int rows;
   bool operator==(const OnlineKey& o) const {
     return x == o.x && ld_x == o.ld_x && B == o.B && sap_start == o.sap_start && sap_end == o.sap_end &&
            thr == o.thr && out == o.out && flags == o.flags && state == o.state && wts == o.wts &&
-           nap_vt == o.nap_vt;
+           nap_vt == o.nap_vt && rows == o.rows;
   }
 };
 // ... of a captured fused train step (mmad_ae_train_step_graph)
@@ -251,9 +253,11 @@ struct mmad_ae {
   // hipGraph cache for mmad_ae_score_stream: one captured graph per
   // (input, output, workspace, N, batch) pass, replayed with one launch
   mmad_ae_impl::GraphCache<mmad_ae_impl::ScoreKey> graphs{8};
-  // the same for mmad_ae_online_score: one captured 16-row pass per call
+  // the same for mmad_ae_online_score / _score64: one captured pass per call
   // signature.  online_ready: the state buffer whose NAP operand this handle
-  // has zeroed (its padding is never written again)
+  // has zeroed (its padding is never written again); a 64-row state is held
+  // as its address + 1 (states are 256-byte aligned), so one buffer carved
+  // both ways, or two states taking turns, are zeroed again at each change
   mmad_ae_impl::GraphCache<mmad_ae_impl::OnlineKey> ographs{8};
   const void* online_ready = nullptr;
   // kernel probe (mmad_ae_probe): timing events around ONE GEMM launch of

@@ -1,23 +1,26 @@
-// ---- online scoring: B <= 16 windows through the 16-row weight stream -------
-// (mmad_skinny.hip).  The batch path (mmad_ae_score.hip) pads such a call to
-// 128 rows and spends its ~30 launches on zeros; here every layer is one launch
-// that reads its weights once.  All buffers live in a caller-owned state, carved below.
+// ---- online scoring: B <= 16 windows through the 16-row weight stream, or
+// B <= 64 through the 64-row one (mmad_skinny.hip).  The batch path
+// (mmad_ae_score.hip) pads such a call to 128 rows and spends its ~30 launches
+// on zeros; here every layer is one launch that reads its weights once.  All
+// buffers live in a caller-owned state, carved below for `rows` = 16 or 64: the
+// two entry points share the carve and the launch list and differ in the row
+// capacity of every buffer and in the two kernels behind it.
 #include "mmad_ae_impl.h"
 
 using namespace mmad_ae_impl;
 
 struct OnlineWS {
-  void* xin = nullptr;             // packed input [16][Kp0]
+  void* xin = nullptr;             // packed input [rows][Kp0]
   std::vector<void*> y, p2;        // pass-1 outputs per layer; pass-2 outputs per encoder layer
   void* zbuf = nullptr;            // VIB: z [128][Kp] as mmad_vib_reparam_fwd writes it
   float *scale = nullptr, *shift = nullptr;   // folded eval-BN constants [n_bn]
-  std::vector<float*> rs;          // row partials per diff layer [Np/16][16]
-  float* nap_x = nullptr;          // packed NAP operand [16][nap.Kp] (fp32)
-  float* nap_rs = nullptr;         // the NAP launch's row partials [Rp/16][16]
+  std::vector<float*> rs;          // row partials per diff layer [Np/16][rows]
+  float* nap_x = nullptr;          // packed NAP operand [rows][nap.Kp] (fp32)
+  float* nap_rs = nullptr;         // the NAP launch's row partials [Rp/16][rows]
   int64_t bytes = 0;
 };
 
-static void online_carve(const mmad_ae* h, char* base, OnlineWS& o) {
+static void online_carve(const mmad_ae* h, char* base, OnlineWS& o, int rows) {
   int64_t off = 0;
   auto take = [&](int64_t bytes) -> char* {
     off = (off + 255) / 256 * 256;
@@ -25,22 +28,22 @@ static void online_carve(const mmad_ae* h, char* base, OnlineWS& o) {
     off += bytes;
     return p;
   };
-  const int64_t E = (int64_t)esz(h->dtype);
+  const int64_t E = (int64_t)esz(h->dtype), R = rows;
   const int nL = (int)h->L.size();
-  o.xin = take(16 * h->L[0].Kp * E);
+  o.xin = take(R * h->L[0].Kp * E);
   o.y.resize(nL);
-  for (int l = 0; l < nL; ++l) o.y[l] = take(16 * h->L[l].Np * E);
+  for (int l = 0; l < nL; ++l) o.y[l] = take(R * h->L[l].Np * E);
   if (h->vib) o.zbuf = take((int64_t)MMAD_PAD * h->L[h->n_enc].Kp * E);
   o.p2.resize(h->n_enc);
-  for (int e = 0; e < h->n_enc; ++e) o.p2[e] = take(16 * h->L[e].Np * E);
+  for (int e = 0; e < h->n_enc; ++e) o.p2[e] = take(R * h->L[e].Np * E);
   o.scale = (float*)take(std::max<int64_t>(h->n_bn, 1) * 4);
   o.shift = (float*)take(std::max<int64_t>(h->n_bn, 1) * 4);
   o.rs.resize(h->n_enc + 1);
-  o.rs[0] = (float*)take((int64_t)h->L[nL - 1].Np * 4);   // [Np/16][16]
-  for (int e = 0; e < h->n_enc; ++e) o.rs[e + 1] = (float*)take((int64_t)h->L[e].Np * 4);
+  o.rs[0] = (float*)take(h->L[nL - 1].Np / 16 * R * 4);   // [Np/16][rows]
+  for (int e = 0; e < h->n_enc; ++e) o.rs[e + 1] = (float*)take(h->L[e].Np / 16 * R * 4);
   if (h->nap.on) {
-    o.nap_x = (float*)take(16 * (int64_t)h->nap.Kp * 4);
-    o.nap_rs = (float*)take((int64_t)h->nap.Rp * 4);
+    o.nap_x = (float*)take(R * h->nap.Kp * 4);
+    o.nap_rs = (float*)take(h->nap.Rp / 16 * R * 4);
   }
   o.bytes = (off + 255) / 256 * 256;
 }
@@ -48,17 +51,25 @@ static void online_carve(const mmad_ae* h, char* base, OnlineWS& o) {
 int64_t mmad_ae_online_state_bytes(const mmad_ae* h) {
   if (!h) return -1;
   OnlineWS o;
-  online_carve(h, nullptr, o);
+  online_carve(h, nullptr, o, 16);
+  return o.bytes;
+}
+
+int64_t mmad_ae_online_state_bytes64(const mmad_ae* h) {
+  if (!h) return -1;
+  OnlineWS o;
+  online_carve(h, nullptr, o, 64);
   return o.bytes;
 }
 
 // the launches of one pass on stream st (eager, or into a capture)
 static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int s1, const float* thr,
-                       float* out, uint8_t* flags, const OnlineWS& o, hipStream_t st) {
+                       float* out, uint8_t* flags, const OnlineWS& o, int rows, hipStream_t st) {
   const int dt = h->dtype;
+  const auto launch = rows == 16 ? mmad_skinny_launch : mmad_skinny_rows_launch;
   const int nL = (int)h->L.size();
   const mmad_ae::NapFit& nf = h->nap;
-  RET_IF(mmad_pack_input(dt, B, h->L[0].K, 16, h->L[0].Kp, x, ld_x, o.xin, st));
+  RET_IF(mmad_pack_input(dt, B, h->L[0].K, rows, h->L[0].Kp, x, ld_x, o.xin, st));
   MmadOnlineFold f{};
   f.n_bn = (int)h->n_bn;
   for (const AeLayer& a : h->L)
@@ -91,7 +102,7 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
       a.rowsq = o.rs[0];
       route(a, 0);
     }
-    RET_IF(mmad_skinny_launch(dt, a, st));
+    RET_IF(launch(dt, a, st));
     if (h->vib && l == h->n_enc - 1)
       RET_IF(mmad_vib_reparam_fwd(dt, B, h->btl, 1, o.y[l], L.Np, nullptr, nullptr, 0, 0, 1, o.zbuf,
                                   h->L[h->n_enc].Kp, nullptr, st));
@@ -104,7 +115,7 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
     a.ref = o.y[e]; a.ref_f32 = 0; a.ldref = L.Np;
     a.rowsq = o.rs[e + 1];
     route(a, e + 1);
-    RET_IF(mmad_skinny_launch(dt, a, st));
+    RET_IF(launch(dt, a, st));
     cur = o.p2[e];
   }
   // the NAP run: the same kernel on the fit's fp32 V^T (K = W, N = R), bias
@@ -114,7 +125,7 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
     a.M = B; a.N = nf.R; a.Np = nf.Rp; a.Kp = nf.Kp;
     a.x = o.nap_x; a.w = nf.vt; a.bias = nf.bias; a.act = MMAD_ACT_NONE;
     a.colw = nf.w; a.rowsq = o.nap_rs;
-    RET_IF(mmad_skinny_launch(MMAD_F32, a, st));
+    RET_IF(launch(MMAD_F32, a, st));
   }
   MmadOnlineFinish fin{};
   fin.B = B; fin.n_diff = h->n_enc + 1;
@@ -125,19 +136,21 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
   fin.sap_start = s0; fin.sap_end = s1;
   if (nf.on) { fin.nap_rs = o.nap_rs; fin.nap_tiles = nf.Rp / 16; fin.nap_scale = 1.f / (float)nf.R; }
   fin.out = out; fin.flags = flags; fin.thresholds = thr;
-  return mmad_online_finish(fin, st);
+  return rows == 16 ? mmad_online_finish(fin, st) : mmad_online_finish64(fin, st);
 }
 
-int mmad_ae_online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
-                         const float* thresholds, float* out, uint8_t* flags, void* state,
-                         int64_t state_bytes, int use_graph, void* stream) {
+// both entry points; rows = 16 (mmad_ae_online_score) or 64 (_score64)
+static int online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
+                        const float* thresholds, float* out, uint8_t* flags, void* state,
+                        int64_t state_bytes, int use_graph, void* stream, int rows) {
   MMAD_CHECK_ARG(h, "ae_online_score: null handle");
-  MMAD_CHECK_ARG(B >= 1 && B <= 16, "ae_online_score: B=%d outside 1..16 (the batch path, "
-                 "mmad_ae_score_stream, serves larger calls)", B);
-  const int64_t need = mmad_ae_online_state_bytes(h);
+  const char* sfx = rows == 16 ? "" : "64";
+  MMAD_CHECK_ARG(B >= 1 && B <= rows, "ae_online_score%s: B=%d outside 1..%d (the batch path, "
+                 "mmad_ae_score_stream, serves larger calls)", sfx, B, rows);
+  const int64_t need = rows == 16 ? mmad_ae_online_state_bytes(h) : mmad_ae_online_state_bytes64(h);
   MMAD_CHECK_ARG(state && state_bytes >= need, "ae_online_score: online state null or too small "
-                 "(%lld < %lld bytes, mmad_ae_online_state_bytes)", (long long)(state ? state_bytes : 0),
-                 (long long)need);
+                 "(%lld < %lld bytes, mmad_ae_online_state_bytes%s)", (long long)(state ? state_bytes : 0),
+                 (long long)need, sfx);
   MMAD_CHECK_ARG(((uintptr_t)state) % 256 == 0, "ae_online_score: state must be 256-byte aligned");
   MMAD_CHECK_ARG(h->params && h->running, "ae_online_score: unbound handle");
   MMAD_CHECK_ARG(x && ld_x >= h->L[0].K && out, "ae_online_score: bad args (null x / out, ld_x=%d)", ld_x);
@@ -155,17 +168,18 @@ int mmad_ae_online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_st
   if (s1 > nd) s1 = nd;
   hipStream_t st = (hipStream_t)stream;
   OnlineWS o;
-  online_carve(h, (char*)state, o);
-  if (h->nap.on && h->online_ready != state) {
-    MMAD_HIP_CHECK(hipMemsetAsync(o.nap_x, 0, 16 * (size_t)h->nap.Kp * 4, st));
-    h->online_ready = state;
+  online_carve(h, (char*)state, o, rows);
+  const void* tag = (const char*)state + (rows == 16 ? 0 : 1);   // mmad_ae::online_ready
+  if (h->nap.on && h->online_ready != tag) {
+    MMAD_HIP_CHECK(hipMemsetAsync(o.nap_x, 0, (size_t)rows * h->nap.Kp * 4, st));
+    h->online_ready = tag;
   }
   auto pass = [&](hipStream_t s) {
-    return online_pass(h, x, ld_x, B, s0, s1, thresholds, out, flags, o, s);
+    return online_pass(h, x, ld_x, B, s0, s1, thresholds, out, flags, o, rows, s);
   };
   if (!use_graph) return pass(st);
   const void* nap_vt = h->nap.on ? (const void*)h->nap.vt : nullptr;
-  const OnlineKey key{x, ld_x, B, s0, s1, thresholds, out, flags, state, weights(h, h->L[0]), nap_vt};
+  const OnlineKey key{x, ld_x, B, s0, s1, thresholds, out, flags, state, weights(h, h->L[0]), nap_vt, rows};
   if (hipGraphExec_t hit = h->ographs.find(key)) {
     MMAD_HIP_CHECK(hipGraphLaunch(hit, st));
     return MMAD_OK;
@@ -175,4 +189,18 @@ int mmad_ae_online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_st
   RET_IF(capture_error(capture_graph(h, pass, &exec)));
   h->ographs.insert(key, exec);   // bounded cache: drops the oldest pass
   return MMAD_OK;
+}
+
+int mmad_ae_online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
+                         const float* thresholds, float* out, uint8_t* flags, void* state,
+                         int64_t state_bytes, int use_graph, void* stream) {
+  return online_score(h, x, ld_x, B, sap_start, sap_end, thresholds, out, flags, state, state_bytes,
+                      use_graph, stream, 16);
+}
+
+int mmad_ae_online_score64(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
+                           const float* thresholds, float* out, uint8_t* flags, void* state,
+                           int64_t state_bytes, int use_graph, void* stream) {
+  return online_score(h, x, ld_x, B, sap_start, sap_end, thresholds, out, flags, state, state_bytes,
+                      use_graph, stream, 64);
 }

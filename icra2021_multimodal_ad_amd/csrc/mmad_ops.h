@@ -43,6 +43,9 @@ struct MmadSkinny {
   float* rowsq;          // [Np/16][16], non-null selects the score epilogue
 };
 int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream);
+// the same for M <= 64 valid rows (mmad_fc_rows64): every [16] above is [64],
+// rowsq [Np/16][64]; ceil(M / 16) row tiles computed, all 64 rows written
+int mmad_skinny_rows_launch(int dtype, const MmadSkinny& a, void* stream);
 
 #define MMAD_ONLINE_MAX_LAYERS 32
 #define MMAD_ONLINE_MAX_DIFF 16
@@ -68,6 +71,8 @@ struct MmadOnlineFinish {
   const float* thresholds;                // [3], nullable
 };
 int mmad_online_finish(const MmadOnlineFinish& f, void* stream);
+// the 64-row form: rs [tiles][64], out [n_diff + 3][64], flags [3][64]
+int mmad_online_finish64(const MmadOnlineFinish& f, void* stream);
 
 #define MMAD_MAX_REDUCE_JOBS 24
 struct MmadReduceJob {

@@ -1,5 +1,6 @@
-// 16-row weight-streaming layer operator (mmad_fc_rows16) and the two small
-// kernels of the online scoring pass (mmad_ae_online_score, mmad_ae_online.hip).
+// 16-row weight-streaming layer operator (mmad_fc_rows16), its form for up to
+// 64 rows (mmad_fc_rows64, skinny_rows_k below) and the small kernels of the
+// online scoring pass (mmad_ae_online_score / _score64, mmad_ae_online.hip).
 //
 // y[16][N] = epi(x[16][K] . W[N][K]^T) for at most 16 valid rows: the work is
 // one pass over W, so the kernel is built as a weight stream, not as a GEMM
@@ -146,6 +147,134 @@ __global__ __launch_bounds__(NW * 64) void skinny_k(const MmadSkinny a) {
   }
 }
 
+// ---- up to 64 rows: RT = ceil(M / 16) row tiles against one weight stream
+// (mmad_fc_rows64).  skinny_k's grid, K-chunk assignment, fragment maps and W
+// loads; a lane loads a chunk's W fragments once and issues one MFMA group per
+// row tile, each with its own A fragments (rows 16 t + (lane & 15) of x) and
+// its own accumulator, so a row's accumulator sees skinny_k's products in
+// skinny_k's order and its bits are those of the same row through skinny_k.
+// W and the RT tiles of x are both loaded a chunk ahead.  Row tiles >= RT are
+// neither loaded nor computed (RT is the instantiation); their rows are
+// written as zero.  The waves' accumulators meet in LDS; wave t adds tile t's
+// in wave order and runs its epilogue (waves beyond NW take t + NW, ...).
+// Packed layouts: x [64][Kp], y [64][Np], diff [64][lddiff], rowsq [Np/16][64].
+constexpr int RTMAX = 4;
+
+template <int RT>
+__device__ __forceinline__ void mma_rows(floatx4 (&acc)[RT], const bf16x8 (&a)[RT][U], const bf16x8 (&b)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int t = 0; t < RT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][u], b[u], acc[t], 0, 0, 0);
+}
+template <int RT>
+__device__ __forceinline__ void mma_rows(floatx4 (&acc)[RT], const floatx4 (&a)[RT][U], const floatx4 (&b)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int t = 0; t < RT; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][u][j], b[u][j], acc[t], 0, 0, 0);
+}
+
+template <typename T, int RT>
+__global__ __launch_bounds__(NW * 64) void skinny_rows_k(const MmadSkinny a) {
+  typedef typename Frag<T>::V V;
+  constexpr int KL = Frag<T>::KL;
+  constexpr int CK = 4 * KL * U;
+  __shared__ floatx4 red[NW][RT][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c16 = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * 16;
+  const T* wp = (const T*)a.w + (size_t)(n0 + c16) * a.Kp + g * KL;
+  const T* xp = (const T*)a.x + (size_t)c16 * a.Kp + g * KL;
+  const size_t xt = (size_t)16 * a.Kp;   // one row tile of x
+  const int nch = a.Kp / CK;
+  floatx4 acc[RT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+  V bw[U], ax[RT][U];
+  int c = wv;
+  if (c < nch) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bw[u] = load_w((const V*)(wp + (size_t)c * CK + u * 4 * KL));
+#pragma unroll
+      for (int t = 0; t < RT; ++t) ax[t][u] = *(const V*)(xp + t * xt + (size_t)c * CK + u * 4 * KL);
+    }
+  }
+  while (c < nch) {
+    V bn[U], an[RT][U];
+    const int cn = c + NW;
+    const bool more = cn < nch;   // wave-uniform
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        bn[u] = load_w((const V*)(wp + (size_t)cn * CK + u * 4 * KL));
+#pragma unroll
+        for (int t = 0; t < RT; ++t) an[t][u] = *(const V*)(xp + t * xt + (size_t)cn * CK + u * 4 * KL);
+      }
+    }
+    mma_rows<RT>(acc, ax, bw);
+    if (!more) break;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bw[u] = bn[u];
+#pragma unroll
+      for (int t = 0; t < RT; ++t) ax[t][u] = an[t][u];
+    }
+    c = cn;
+  }
+#pragma unroll
+  for (int t = 0; t < RT; ++t) red[wv][t][lane] = acc[t];
+  __syncthreads();
+
+  // ---- epilogue of row tile t: column n, rows 16 t + 4 g + r
+  const int n = n0 + c16;
+  const bool nv = n < a.N;
+  const float b = a.bias ? a.bias[n] : 0.f;
+  const float sc = a.scale ? a.scale[n] : 1.f;
+  const float sh = a.shift ? a.shift[n] : 0.f;
+  const float cw = a.colw ? a.colw[n] : 1.f;
+  for (int t = wv; t < RTMAX; t += NW) {
+    floatx4 s = {0.f, 0.f, 0.f, 0.f};   // tiles >= RT: every row is >= M
+    if (t < RT) {
+      s = red[0][t][lane];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) s += red[w][t][lane];
+    }
+    float sq[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = 16 * t + 4 * g + r;
+      const bool valid = nv && m < a.M;
+      float v = apply_act(s[r] + b, a.act, a.slope);
+      if (a.scale) v = v * sc + sh;
+      v = valid ? v : 0.f;
+      if (a.y) ((T*)a.y)[(size_t)m * a.Np + n] = from_f32<T>(v);
+      sq[r] = 0.f;
+      if (a.rowsq) {
+        float rf = 0.f;
+        if (a.ref && valid)
+          rf = a.ref_f32 ? ((const float*)a.ref)[(size_t)m * a.ldref + n]
+                         : to_f32<T>(((const T*)a.ref)[(size_t)m * a.ldref + n]);
+        const float d = v - rf;   // invalid: 0 - 0
+        if (a.diff && nv) a.diff[(size_t)m * a.lddiff + n] = d;
+        sq[r] = d * d * cw;
+      }
+    }
+    if (a.rowsq) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) sq[r] += __shfl_xor(sq[r], o);
+        if (c16 == 0) a.rowsq[(size_t)blockIdx.x * 64 + 16 * t + 4 * g + r] = sq[r];
+      }
+    }
+  }
+}
+
 // eval-BN (scale, shift) of every BN layer in one grid (mmad_bn_eval_affine
 // per layer): element j of the [n_bn] running-stat layout
 __global__ __launch_bounds__(256) void online_fold_k(const MmadOnlineFold f, const float* __restrict__ params,
@@ -212,6 +341,64 @@ __global__ __launch_bounds__(320) void online_finish_k(const MmadOnlineFinish f)
   }
 }
 
+// online_finish_k for the 64-row layouts: rs [tiles][64], out [n_diff + 3][64],
+// flags [3][64]; the same left-to-right tile sum per (layer, row)
+__global__ __launch_bounds__(512) void online_finish64_k(const MmadOnlineFinish f) {
+  __shared__ float lsq[MMAD_ONLINE_MAX_DIFF + 1][64];
+  const int b = threadIdx.x & 63;
+  for (int j = threadIdx.x >> 6; j < f.n_diff + (f.nap_rs ? 1 : 0); j += 8) {
+    const float* p = j < f.n_diff ? f.rs[j] : f.nap_rs;
+    const int nt = j < f.n_diff ? f.tiles[j] : f.nap_tiles;
+    float s = 0.f;
+    int t = 0;
+    for (; t + 8 <= nt; t += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(t + u) * 64 + b];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; t < nt; ++t) s += p[(size_t)t * 64 + b];
+    lsq[j][b] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x >= 64 || b >= f.B) return;
+  float* out = f.out;
+  for (int l = 0; l < f.n_diff; ++l) out[l * 64 + b] = lsq[l][b];
+  const float base = lsq[0][b] / (float)f.widths[0];
+  float ss = 0.f;
+  int wsum = 0;
+  for (int l = f.sap_start; l < f.sap_end; ++l) {
+    ss += lsq[l][b];
+    wsum += f.widths[l];
+  }
+  const float sap = ss / (float)wsum;
+  out[f.n_diff * 64 + b] = base;
+  out[(f.n_diff + 1) * 64 + b] = sap;
+  float nap = 0.f;
+  if (f.nap_rs) {
+    nap = lsq[f.n_diff][b] * f.nap_scale;
+    out[(f.n_diff + 2) * 64 + b] = nap;
+  }
+  if (f.flags) {
+    const float* th = f.thresholds;
+    f.flags[b] = th ? (uint8_t)(base > th[0]) : 0;
+    f.flags[64 + b] = th ? (uint8_t)(sap > th[1]) : 0;
+    f.flags[128 + b] = (th && f.nap_rs) ? (uint8_t)(nap > th[2]) : 0;
+  }
+}
+
+template <typename T>
+void launch_rows(const MmadSkinny& a, hipStream_t s) {
+  const dim3 grid(a.Np / 16), block(NW * 64);
+  switch ((a.M + 15) / 16) {
+    case 1: skinny_rows_k<T, 1><<<grid, block, 0, s>>>(a); break;
+    case 2: skinny_rows_k<T, 2><<<grid, block, 0, s>>>(a); break;
+    case 3: skinny_rows_k<T, 3><<<grid, block, 0, s>>>(a); break;
+    default: skinny_rows_k<T, 4><<<grid, block, 0, s>>>(a); break;
+  }
+}
+
 }  // namespace
 
 int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream) {
@@ -255,6 +442,46 @@ int mmad_fc_rows16(int dtype, int M, int N, int K, int Np, int Kp, const void* x
   return mmad_skinny_launch(dtype, a, stream);
 }
 
+int mmad_skinny_rows_launch(int dtype, const MmadSkinny& a, void* stream) {
+  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16, "fc_rows64: dtype %d (MMAD_F32 or MMAD_BF16)", dtype);
+  MMAD_CHECK_ARG(a.M >= 1 && a.M <= 16 * RTMAX, "fc_rows64: M=%d outside 1..64", a.M);
+  MMAD_CHECK_ARG(a.N >= 1 && a.N <= a.Np && a.Np % 16 == 0 && a.Kp >= MMAD_PAD && a.Kp % MMAD_PAD == 0,
+                 "fc_rows64: bad sizes N=%d Np=%d Kp=%d (Np a multiple of 16, Kp of %d)", a.N, a.Np, a.Kp,
+                 MMAD_PAD);
+  MMAD_CHECK_ARG(a.x && a.w && ((uintptr_t)a.x | (uintptr_t)a.w) % 16 == 0,
+                 "fc_rows64: x and w must be non-null and 16-byte aligned");
+  MMAD_CHECK_ARG(a.y || a.rowsq, "fc_rows64: neither y nor rowsq to write");
+  MMAD_CHECK_ARG(a.rowsq || (!a.ref && !a.diff && !a.colw), "fc_rows64: ref / diff / colw need rowsq");
+  if (a.act < MMAD_ACT_NONE || a.act > MMAD_ACT_TANH) {
+    mmad_set_error("fc_rows64: activation %d has no per-element epilogue", a.act);
+    return MMAD_EUNSUPPORTED;
+  }
+  if (dtype == MMAD_BF16)
+    launch_rows<bf16>(a, (hipStream_t)stream);
+  else
+    launch_rows<float>(a, (hipStream_t)stream);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
+int mmad_fc_rows64(int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
+                   const float* bias, int act, float slope, const float* bn_scale, const float* bn_shift,
+                   void* y, const void* ref, int ref_dtype, int ldref, float* diff, int lddiff,
+                   const float* colw, float* rowsq, void* stream) {
+  MMAD_CHECK_ARG(K >= 1 && K <= Kp, "fc_rows64: K=%d outside 1..Kp=%d", K, Kp);
+  MMAD_CHECK_ARG(!bn_scale == !bn_shift, "fc_rows64: bn_scale and bn_shift go together");
+  MMAD_CHECK_ARG(!ref || ((ref_dtype == MMAD_F32 || ref_dtype == dtype) && ldref >= N),
+                 "fc_rows64: ref is fp32 or the operand dtype, ldref >= N");
+  MMAD_CHECK_ARG(!diff || lddiff >= N, "fc_rows64: lddiff < N");
+  MmadSkinny a{};
+  a.M = M; a.N = N; a.Np = Np; a.Kp = Kp;
+  a.x = x; a.w = w; a.bias = bias; a.act = act; a.slope = slope;
+  a.scale = bn_scale; a.shift = bn_shift; a.y = y;
+  a.ref = ref; a.ref_f32 = ref_dtype == MMAD_F32; a.ldref = ldref;
+  a.diff = diff; a.lddiff = lddiff; a.colw = colw; a.rowsq = rowsq;
+  return mmad_skinny_rows_launch(dtype, a, stream);
+}
+
 int mmad_online_fold(const MmadOnlineFold& f, const float* params, const float* running, float eps,
                      float* scale, float* shift, void* stream) {
   if (f.n_bn == 0) return MMAD_OK;
@@ -266,6 +493,13 @@ int mmad_online_fold(const MmadOnlineFold& f, const float* params, const float* 
 int mmad_online_finish(const MmadOnlineFinish& f, void* stream) {
   MMAD_CHECK_ARG(f.n_diff >= 1 && f.n_diff <= MMAD_ONLINE_MAX_DIFF, "online_finish: %d diff layers", f.n_diff);
   online_finish_k<<<1, 320, 0, (hipStream_t)stream>>>(f);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
+int mmad_online_finish64(const MmadOnlineFinish& f, void* stream) {
+  MMAD_CHECK_ARG(f.n_diff >= 1 && f.n_diff <= MMAD_ONLINE_MAX_DIFF, "online_finish: %d diff layers", f.n_diff);
+  online_finish64_k<<<1, 512, 0, (hipStream_t)stream>>>(f);
   MMAD_LAUNCH_CHECK();
   return MMAD_OK;
 }

@@ -520,22 +520,31 @@ class NativeAE:
              ptr(out["v"]), ptr(out["mu_s"]), ptr(out["var"]), sp, sb, ws, need, stream_ptr())
         return out, state
 
-    def online_state(self):
-        """A state buffer for online_score (mmad_ae_online_state_bytes): uint8
-        on this device, sized for the handle as it stands (dtype, attached
-        fit); the caller keeps it and passes it to every call."""
-        need = int(self._lib.mmad_ae_online_state_bytes(self._h))
+    @staticmethod
+    def _online_sfx(rows):
+        if rows not in (16, 64):
+            raise ValueError(f"online scoring: rows={rows!r} (16 or 64)")
+        return "" if rows == 16 else "64"
+
+    def online_state(self, rows=16):
+        """A state buffer for online_score (mmad_ae_online_state_bytes, or
+        _bytes64 for rows=64): uint8 on this device, sized for the handle as it
+        stands (dtype, attached fit); the caller keeps it and passes it to
+        every call with the same ``rows``."""
+        need = int(getattr(self._lib, "mmad_ae_online_state_bytes" + self._online_sfx(rows))(self._h))
         if need < 0:
             raise _native.NativeError("online state size query failed")
         return torch.zeros(need + 256, dtype=torch.uint8, device=self.device)
 
     def online_score(self, x, B, out, state, flags=None, thresholds=None, start=0, end=None,
-                     graph=True):
-        """Scores of B <= 16 windows now (mmad_ae_online_score): x fp32 [>=B, D]
-        on this device, out fp32 [n_enc+4, 16] (layer_sq rows, BASE, SAP, NAP),
-        flags uint8 [3, 16] and thresholds fp32 [3] optional device tensors,
-        state from online_state().  With graph=True a repeated call (the same
+                     graph=True, rows=16):
+        """Scores of B <= rows windows now (mmad_ae_online_score; rows=64:
+        mmad_ae_online_score64): x fp32 [>=B, D] on this device, out fp32
+        [n_enc+4, rows] (layer_sq rows, BASE, SAP, NAP), flags uint8 [3, rows]
+        and thresholds fp32 [3] optional device tensors, state from
+        online_state(rows).  With graph=True a repeated call (the same
         tensors) replays one captured hipGraph."""
+        sfx = self._online_sfx(rows)
         self._require(x)
         if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or \
                 x.shape[1] != self.enc_widths[0]:
@@ -543,11 +552,11 @@ class NativeAE:
         if int(B) > x.shape[0]:
             raise ValueError(f"online_score: B={B} > the {x.shape[0]} rows of x")
         if out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() \
-                or tuple(out.shape) != (self.n_enc + 4, 16):
-            raise ValueError("online_score: out must be contiguous fp32 [n_enc+4, 16] on the model device")
+                or tuple(out.shape) != (self.n_enc + 4, rows):
+            raise ValueError(f"online_score: out must be contiguous fp32 [n_enc+4, {rows}] on the model device")
         if flags is not None and (flags.device != self.device or flags.dtype != torch.uint8
-                                  or not flags.is_contiguous() or tuple(flags.shape) != (3, 16)):
-            raise ValueError("online_score: flags must be contiguous uint8 [3, 16] on the model device")
+                                  or not flags.is_contiguous() or tuple(flags.shape) != (3, rows)):
+            raise ValueError(f"online_score: flags must be contiguous uint8 [3, {rows}] on the model device")
         if thresholds is not None and (thresholds.device != self.device or thresholds.dtype != torch.float32
                                        or not thresholds.is_contiguous() or thresholds.numel() != 3):
             raise ValueError("online_score: thresholds must be contiguous fp32 [3] on the model device")
@@ -555,7 +564,7 @@ class NativeAE:
         base = state.data_ptr()
         aligned = (base + 255) // 256 * 256
         end = self.n_enc + 2 if end is None else int(end)
-        call("mmad_ae_online_score", self._h, ptr(x), x.stride(0), int(B), int(start), end,
+        call("mmad_ae_online_score" + sfx, self._h, ptr(x), x.stride(0), int(B), int(start), end,
              ptr(thresholds), ptr(out), ptr(flags), ctypes.c_void_p(aligned),
              state.numel() - (aligned - base), 1 if graph else 0, stream_ptr())
         return out

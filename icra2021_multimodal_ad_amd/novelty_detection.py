@@ -154,21 +154,25 @@ class NoveltyDetecter:
             del nm
         return out
 
-    def online_scorer(self, model, train_x, valid_x):
+    def online_scorer(self, model, train_x, valid_x, rows=None):
         """The deployment form of ``scores``: an online.OnlineScorer over
-        ``model`` that returns BASE, SAP and NAP of up to 16 windows per call
-        from one replayed graph.  NAP is fitted on ``train_x`` as ``scores``
+        ``model`` that returns BASE, SAP and NAP of up to ``rows`` (16 or 64)
+        windows per call from one replayed graph.  rows=None: 16, or 64 when
+        ``config.slicing_size`` (the deployment loop's window count) is
+        17..64.  NAP is fitted on ``train_x`` as ``scores``
         fits it (``config.nap_fit_stream`` honoured); for a bf16 model the
         whole online path runs on the fp32 twin of ``_nap_model`` (NAP needs
         fp32 diffs and one graph is to produce all three scores).  The
         thresholds are calibrated on ``valid_x`` (metric.threshold_metrics'
         quantile rule on the batch route's validation scores).  Single
         process."""
-        from .online import OnlineScorer
+        from .online import OnlineScorer, rows_for
         cfg = self.config
         model.eval()
         start = getattr(cfg, "start_layer_index", 0)
         end = cfg.n_layers + 1 - getattr(cfg, "end_layer_index", -1)
+        if rows is None:
+            rows = rows_for(getattr(cfg, "slicing_size", None))
         with torch.no_grad():
             nm = _nap_model(model, cfg)
             nat = nm._native
@@ -186,7 +190,7 @@ class NoveltyDetecter:
             lv = _layer_sq(nm, valid_x, 698).t().contiguous().t()
             valid = {"base": base_from_layer_sq(lv, widths), "sap": sap_from_layer_sq(lv, widths, start, end),
                      "nap": nap.score(_device_diffs(nm, valid_x, 698)[:, sel])}
-            scorer = OnlineScorer(nm, nap=nap, start_layer_index=start, end_layer_index=end)
+            scorer = OnlineScorer(nm, nap=nap, start_layer_index=start, end_layer_index=end, rows=rows)
             scorer.calibrate(valid)
         return scorer
 

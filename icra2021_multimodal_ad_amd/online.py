@@ -3,30 +3,48 @@
 The reference's deployment loop (test_file/realtime_tester.py:291-309,
 get_realtime_dataloader) fuses the latest 10 sensor windows and asks for their
 scores, over and over.  ``OnlineScorer`` is the object that loop calls: it owns
-a fixed device input buffer [16, D], the outputs, the threshold buffer and the
+a fixed device input buffer [rows, D], the outputs, the threshold buffer and the
 native state (mmad_ae_online_state_bytes), so every call after the first is one
 replayed hipGraph of about 20 short weight-streaming launches
-(mmad_ae_online_score; DESIGN.md §4 "Online scoring").  More than 16 windows
-are the batch route's (reconstruction_aggregation.score_windows).
+(mmad_ae_online_score; DESIGN.md §4 "Online scoring").  ``rows`` is 16 (the
+default) or 64 (mmad_ae_online_score64: up to four 16-row tiles against one
+weight stream, every window's scores the bits of the 16-row path's).  More
+windows than ``rows`` are the batch route's
+(reconstruction_aggregation.score_windows).
 """
 import numpy as np
 import torch
 
 from . import metric
 
-ROWS = 16
+ROWS = 16            # the default row capacity
+ROW_CAPACITIES = (16, 64)
 METHODS = ("base", "sap", "nap")
 
 
+def rows_for(n_windows):
+    """The row capacity for a loop that scores ``n_windows`` (None: unknown)
+    windows a call: 64 for 17..64, else the 16-row default (at <= 16 windows
+    the two are level within the measurement spread and the 16-row state is
+    a quarter of the size: DESIGN.md §4 "Online scoring"; beyond 64 no
+    capacity fits and the scorer names the batch route)."""
+    return 64 if 16 < int(n_windows or 0) <= 64 else ROWS
+
+
 class OnlineScorer:
-    def __init__(self, model, nap=None, start_layer_index=0, end_layer_index=None, thresholds=None):
+    def __init__(self, model, nap=None, start_layer_index=0, end_layer_index=None, thresholds=None,
+                 rows=ROWS):
         """model: an eval-mode autoencoder of the plugin surface (fp32 or bf16,
         no split-bf16 score planes).  nap: a fitted NapScorer (its fit is
         attached to ``model`` for this object's lifetime; a standalone scorer
         is taken to cover the SAP layer range) or None (no NAP score).
         start / end_layer_index: the SAP layer range as
         ``sap_from_layer_sq`` takes it.  thresholds: {'base','sap','nap'} ->
-        float, or None (NaN: no flag until ``calibrate``)."""
+        float, or None (NaN: no flag until ``calibrate``).  rows: 16 or 64,
+        the most windows a call takes (the size of every buffer here)."""
+        if rows not in ROW_CAPACITIES:
+            raise ValueError(f"OnlineScorer: rows={rows!r} (16 or 64)")
+        self.rows = rows
         nat = model._native
         model.eval()
         self.model, self.nat, self.nap = model, nat, nap
@@ -41,11 +59,11 @@ class OnlineScorer:
                 layers = (s, e)
             nap.attach(model, precision="f32", layers=layers)
         dev = nat.device
-        self.x = torch.zeros((ROWS, nat.enc_widths[0]), device=dev)
-        self.out = torch.zeros((nat.n_enc + 4, ROWS), device=dev)
-        self.flags = torch.zeros((3, ROWS), device=dev, dtype=torch.uint8)
+        self.x = torch.zeros((rows, nat.enc_widths[0]), device=dev)
+        self.out = torch.zeros((nat.n_enc + 4, rows), device=dev)
+        self.flags = torch.zeros((3, rows), device=dev, dtype=torch.uint8)
         self.thresholds = torch.full((3,), float("nan"), device=dev)
-        self.state = nat.online_state()
+        self.state = nat.online_state(rows)
         if thresholds is not None:
             self.set_thresholds(thresholds)
 
@@ -72,34 +90,35 @@ class OnlineScorer:
     def _run(self, B):
         n_enc = self.nat.n_enc
         self.nat.online_score(self.x, B, self.out, self.state, flags=self.flags,
-                              thresholds=self.thresholds, start=self.start, end=self.end)
+                              thresholds=self.thresholds, start=self.start, end=self.end,
+                              rows=self.rows)
         return {"layer_sq": self.out[:n_enc + 1, :B], "base": self.out[n_enc + 1, :B],
                 "sap": self.out[n_enc + 2, :B],
                 "nap": self.out[n_enc + 3, :B] if self.nap is not None else None,
                 "flags": self.flags[:, :B]}
 
     def score(self, x):
-        """x: [B <= 16, D], host or device.  Returns {'base','sap','nap',
+        """x: [B <= rows, D], host or device.  Returns {'base','sap','nap',
         'layer_sq','flags'}: views of this object's fixed outputs on the
         device, rewritten by the next call (copy what you keep)."""
         x = torch.as_tensor(x)
         x = x.reshape(x.shape[0], -1)
         B = x.shape[0]
-        if B > ROWS:
-            raise ValueError(f"OnlineScorer.score: {B} windows > {ROWS}; score_windows "
+        if B > self.rows:
+            raise ValueError(f"OnlineScorer.score: {B} windows > {self.rows}; score_windows "
                              "(reconstruction_aggregation) is the batch route")
         if B < 1 or x.shape[1] != self.x.shape[1]:
-            raise ValueError(f"OnlineScorer.score: x must be [1..{ROWS}, {self.x.shape[1]}], got {tuple(x.shape)}")
+            raise ValueError(f"OnlineScorer.score: x must be [1..{self.rows}, {self.x.shape[1]}], got {tuple(x.shape)}")
         self.x[:B].copy_(x, non_blocking=True)
         return self._run(B)
 
     def score_frames(self, hsr_net, r, d, t, m):
         """One step of get_realtime_dataloader: HSR_Net.forward (mmad_hsr_fuse)
-        of the latest ``hsr_net.batch_size`` <= 16 frames straight into the
+        of the latest ``hsr_net.batch_size`` <= rows frames straight into the
         fixed input buffer, on the same stream, then ``score``'s pass."""
         B = int(hsr_net.batch_size)
-        if B > ROWS:
-            raise ValueError(f"OnlineScorer.score_frames: slicing_size {B} > {ROWS}; score_windows "
+        if B > self.rows:
+            raise ValueError(f"OnlineScorer.score_frames: slicing_size {B} > {self.rows}; score_windows "
                              "(reconstruction_aggregation) is the batch route")
         fused = hsr_net.forward(r, d, None, t, m, out=self.x)
         if fused.reshape(B, -1).shape[1] != self.x.shape[1]:

@@ -219,6 +219,19 @@ int mmad_fc_rows16(int dtype, int M, int N, int K, int Np, int Kp, const void* x
                    const float* bn_shift, void* y, const void* ref, int ref_dtype, int ldref,
                    float* diff, int lddiff, const float* colw, float* rowsq, void* stream);
 
+/* The same operator for M in 1..64 rows: ceil(M / 16) row tiles against ONE
+ * stream of w (a lane loads a chunk's weight fragments once and issues one
+ * MFMA group per row tile).  Arguments and refusals as mmad_fc_rows16, with
+ * 64-row layouts: x packed [64][Kp] (rows >= M zero), y [64][Np], diff fp32
+ * [64][lddiff], rowsq fp32 [Np/16][64]; rows M..63 of y, diff (columns < N) and
+ * rowsq are written 0, nothing beyond row 63.  Row i of the result equals, bit
+ * for bit, the same row pushed through mmad_fc_rows16 in any 16-row group:
+ * every row's accumulator sees the same products in the same order. */
+int mmad_fc_rows64(int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
+                   const float* bias, int act, float slope, const float* bn_scale,
+                   const float* bn_shift, void* y, const void* ref, int ref_dtype, int ldref,
+                   float* diff, int lddiff, const float* colw, float* rowsq, void* stream);
+
 /* BatchNorm1d eval affine (layers/fc_layer.py:33): scale = gamma/sqrt(rv+eps),
  * shift = beta - rm*scale, for N columns (padded columns -> 0). */
 int mmad_bn_eval_affine(int N, int Np, const float* gamma, const float* beta, const float* rm,
@@ -771,6 +784,23 @@ int64_t mmad_ae_online_state_bytes(const mmad_ae* h);
 int mmad_ae_online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
                          const float* thresholds, float* out, uint8_t* flags, void* state,
                          int64_t state_bytes, int use_graph, void* stream);
+
+/* The online pass for B in 1..64 windows (mmad_fc_rows64 per layer): the same
+ * launch list, scores and refusals as mmad_ae_online_score, with every 16 of
+ * its layouts a 64.  state: mmad_ae_online_state_bytes64(h) bytes (the packed
+ * input, every layer's 64-row outputs, pass-2 outputs, folded BN constants,
+ * row partials [Np/16][64] and, with a fit attached, the NAP operand [64][Kp]
+ * and its partials); out fp32 [n_enc + 4][64], flags uint8 [3][64], columns
+ * >= B untouched.  Window i's scores and flags equal, bit for bit, those of
+ * mmad_ae_online_score on any group of <= 16 windows that holds it.  The
+ * captured passes share the handle's 8 online graphs with the 16-row entry
+ * point; the row capacity is part of a pass's signature, and a 16-row and a
+ * 64-row state may take turns on one handle.
+ * MMAD_EINVAL, nothing launched: B outside 1..64, else as above. */
+int64_t mmad_ae_online_state_bytes64(const mmad_ae* h);
+int mmad_ae_online_score64(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
+                           const float* thresholds, float* out, uint8_t* flags, void* state,
+                           int64_t state_bytes, int use_graph, void* stream);
 
 /* Split-K health of the executor workspace `ws` (as mmad_gemm_status): a
  * no-op returning MMAD_OK unless split-K is enabled (tuning knob 4 > 1);

@@ -17,7 +17,17 @@ once (AE weights + the encoder again + V^T) / 8 TB/s.
   python tools/online_latency.py [--out profiles/online_latency.json]
   python tools/online_latency.py --variant TAG --out FILE   # (c) / (c0) only, merged
       into FILE under "variants": a library built with other compile-time
-      constants (MMAD_LIB=...: -DMMAD_SKINNY_NT=1, -DMMAD_SKINNY_WAVES=8)"""
+      constants (MMAD_LIB=...: -DMMAD_SKINNY_NT=1, -DMMAD_SKINNY_WAVES=8)
+  python tools/online_latency.py --rows64 [--out profiles/online_rows64_latency.json]
+      the 64-row route (mmad_ae_online_score64): B = 10, 16, 17, 32, 64 on both
+      handles, with the fit and without, each B's routes alternated in one
+      process with the same warm-up and call counts:
+        (b)   mmad_ae_score_nap_stream (without a fit: mmad_ae_score_stream),
+              N = batch = B, graph-replayed
+        (c16) mmad_ae_online_score, replayed, where B <= 16
+        (c64) mmad_ae_online_score64, replayed
+      and the two comparisons the documents rest on: c64 / b at every B, c64 /
+      c16 at B <= 16 (a route is the faster one beyond the 3 % spread)."""
 import argparse
 import ctypes
 import json
@@ -138,12 +148,98 @@ def run_case(dtype, B, variant):
     return res
 
 
+ROWS64_B = (10, 16, 17, 32, 64)
+SPREAD = 0.03   # box-to-box spread: a ratio inside 1 +- SPREAD decides nothing
+
+
+def run_rows64(dtype):
+    lib = _native.load()
+    m = build(dtype)
+    nat = m._native
+    h, s = nat._h, stream_ptr()
+    D, n = nat.enc_widths[0], nat.n_enc
+    x = torch.randn((64, D), device="cuda")
+    thr = torch.ones(3, device="cuda")
+    outs = {r: torch.zeros((n + 4, r), device="cuda") for r in (16, 64)}
+    flags = {r: torch.zeros((3, r), device="cuda", dtype=torch.uint8) for r in (16, 64)}
+    nat.sync_shadow()
+
+    def online(rows, B, state):
+        base = state.data_ptr()
+        al = (base + 255) // 256 * 256
+        name = "mmad_ae_online_score" + ("" if rows == 16 else "64")
+        fn_, args = getattr(lib, name), (h, ptr(x), D, B, 0, n + 2, ptr(thr), ptr(outs[rows]), ptr(flags[rows]),
+                                         ctypes.c_void_p(al), state.numel() - (al - base), 1, s)
+        return lambda: _native.check(fn_(*args), name)
+
+    cases = {}
+    for with_nap in (False, True):
+        if with_nap:
+            fit = random_fit(nat)
+            nat.set_nap(fit)
+        states = {r: nat.online_state(r) for r in (16, 64)}   # sized for the handle as it stands
+        for B in ROWS64_B:
+            ws, nb = nat.workspace(B, 1)
+            lsq = torch.zeros((n + 1, B), device="cuda")
+            nap = torch.zeros(B, device="cuda")
+            if with_nap:
+                b_args = (h, ptr(x), D, B, B, ptr(lsq), B, ptr(nap), ws, nb, 1, s)
+                b_fn = lambda a_=b_args: _native.check(lib.mmad_ae_score_nap_stream(*a_), "b")
+            else:
+                b_args = (h, ptr(x), D, B, B, ptr(lsq), B, ws, nb, 1, s)
+                b_fn = lambda a_=b_args: _native.check(lib.mmad_ae_score_stream(*a_), "b")
+            fns = {"b_batch_stream_graph": b_fn}
+            if B <= 16:
+                fns["c16_online"] = online(16, B, states[16])
+            fns["c64_online"] = online(64, B, states[64])
+            res = measure(fns)
+            assert torch.isfinite(outs[64][:n + 3, :B]).all() and torch.isfinite(lsq).all()
+            # the two routes' layer sums agree (fp32: another summation order; bf16: its rounding)
+            rel = float(((outs[64][:n + 1, :B] - lsq).abs().max() / lsq.abs().max()).item())
+            assert rel < (1e-3 if dtype == "f32" else 1e-1), rel
+            if B <= 16:
+                assert torch.equal(outs[64][:n + 3, :B], outs[16][:n + 3, :B])
+            med = {k: v["gpu"]["median_us"] for k, v in res.items()}
+            res["c64_vs_b_gpu"] = med["c64_online"] / med["b_batch_stream_graph"]
+            if B <= 16:
+                res["c64_vs_c16_gpu"] = med["c64_online"] / med["c16_online"]
+            res["layer_sq_max_rel_diff_c64_vs_b"] = rel
+            res["weight_stream_bound_us"] = stream_bytes(nat, with_nap) / HBM_BYTES_PER_S * 1e6
+            cases[f"{dtype}_{'nap' if with_nap else 'nonap'}_B{B}"] = res
+            print(f"{dtype} nap={int(with_nap)} B={B}", {k: round(v, 1) for k, v in med.items()}, flush=True)
+    nat.set_nap(None)
+    return cases
+
+
+def main_rows64(out):
+    cases = {}
+    for dt in ("f32", "bf16"):
+        cases.update(run_rows64(dt))
+    faster_than_b = {}
+    for dt in ("f32", "bf16"):
+        for tag in ("nap", "nonap"):
+            faster_than_b[f"{dt}_{tag}"] = [B for B in ROWS64_B
+                                            if cases[f"{dt}_{tag}_B{B}"]["c64_vs_b_gpu"] < 1 - SPREAD]
+    doc = {"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "calls": CALLS,
+           "hbm_bytes_per_s": HBM_BYTES_PER_S, "spread": SPREAD, "cases": cases,
+           "c64_faster_than_b_at_B": faster_than_b,
+           "c64_slower_than_c16_at_B": {k: c["c64_vs_c16_gpu"] for k, c in cases.items()
+                                        if c.get("c64_vs_c16_gpu", 0) > 1 + SPREAD}}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/online_latency.json")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--variant", default=None)
+    ap.add_argument("--rows64", action="store_true")
     a = ap.parse_args()
     _native.require_gpu()
+    if a.rows64:
+        return main_rows64(a.out or "profiles/online_rows64_latency.json")
+    a.out = a.out or "profiles/online_latency.json"
     cases = {f"{dt}_B{B}": run_case(dt, B, a.variant) for dt in ("f32", "bf16") for B in (10, 16)}
     if a.variant:
         doc = json.load(open(a.out))
