@@ -16,6 +16,7 @@ MMAD_EINVAL, MMAD_EUNSUPPORTED, MMAD_EHIP, MMAD_ERCCL = -1, -2, -3, -4
 F32, BF16 = 0, 1
 BF16X3 = 2   # split-bf16 planes: eval / score path only (include/mmad.h)
 ACT = {None: 0, "leakyrelu": 1, "relu": 2, "sigmoid": 3, "tanh": 4}
+MAX_GROUPS = 8   # MMAD_MAX_GROUPS: column groups of one mmad_group_sq call
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -47,6 +48,10 @@ SIGNATURES = {
                             _P, _P, _P]),
     "mmad_ae_online_state_bytes64": (_I64, [_P]),
     "mmad_ae_online_score64": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _I, _P]),
+    "mmad_group_sq": (_I, [_I64, _P, _I64, ctypes.POINTER(_I), _I, _P, _P, _I64, _P, _I64, _P]),
+    "mmad_ae_online_groups_bytes": (_I64, [_P, _I]),
+    "mmad_ae_online_score_groups": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _I, _P,
+                                         _I, ctypes.POINTER(_I), _I, _P, _P, _P, _P, _I64]),
     "mmad_bn_eval_affine": (_I, [_I, _I, _P, _P, _P, _P, _F, _P, _P, _P]),
     "mmad_bn_train_apply": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P,
                                  _P]),

@@ -77,15 +77,22 @@ struct ScoreKey {
   }
 };
 // ... of a captured mmad_ae_online_score / mmad_ae_online_score64 pass; rows:
-// the entry point's row capacity (16 / 64: other kernels, other layouts)
+// the entry point's row capacity (16 / 64: other kernels, other layouts).  A
+// grouped pass (mmad_ae_online_score_groups) adds G > 0, the bounds' values
+// (zero beyond G) and its buffers; an ungrouped one leaves them all zero
 struct OnlineKey {
   const float* x; int ld_x, B, sap_start, sap_end; const float* thr; float* out; uint8_t* flags;
   void* state; const void* wts; const void* nap_vt;
   int rows;
+  int G = 0;
+  int bounds[MMAD_MAX_GROUPS + 1] = {};
+  const float* gthr = nullptr; float* gout = nullptr; uint8_t* gflags = nullptr; void* gstate = nullptr;
   bool operator==(const OnlineKey& o) const {
     return x == o.x && ld_x == o.ld_x && B == o.B && sap_start == o.sap_start && sap_end == o.sap_end &&
            thr == o.thr && out == o.out && flags == o.flags && state == o.state && wts == o.wts &&
-           nap_vt == o.nap_vt && rows == o.rows;
+           nap_vt == o.nap_vt && rows == o.rows && G == o.G &&
+           std::equal(bounds, bounds + MMAD_MAX_GROUPS + 1, o.bounds) && gthr == o.gthr &&
+           gout == o.gout && gflags == o.gflags && gstate == o.gstate;
   }
 };
 // ... of a captured fused train step (mmad_ae_train_step_graph)

@@ -62,9 +62,21 @@ int64_t mmad_ae_online_state_bytes64(const mmad_ae* h) {
   return o.bytes;
 }
 
-// the launches of one pass on stream st (eager, or into a capture)
+// per-modality scores of a grouped pass (mmad_ae_online_score_groups)
+struct OnlineGroups {
+  int G;
+  int bounds[MMAD_MAX_GROUPS + 1];
+  const float* thr;   // [G], nullable
+  float* out;         // [G][rows]
+  uint8_t* flags;     // [G][rows], nullable
+  float* d0;          // the groups buffer [rows][Kp0]
+};
+
+// the launches of one pass on stream st (eager, or into a capture); gr: null,
+// or the groups of a grouped pass -- one more launch, nothing else moves
 static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int s1, const float* thr,
-                       float* out, uint8_t* flags, const OnlineWS& o, int rows, hipStream_t st) {
+                       float* out, uint8_t* flags, const OnlineWS& o, int rows, hipStream_t st,
+                       const OnlineGroups* gr = nullptr) {
   const int dt = h->dtype;
   const auto launch = rows == 16 ? mmad_skinny_launch : mmad_skinny_rows_launch;
   const int nL = (int)h->L.size();
@@ -92,6 +104,8 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
     a.y = y;
     return a;
   };
+  const float* d0 = nullptr;   // grouped pass: where the last decoder launch leaves d0
+  int ldd0 = 0;
   // pass 1: eval forward; the decoder's last layer scores d0 = x_hat - x
   for (int l = 0; l < nL; ++l) {
     const AeLayer& L = h->L[l];
@@ -101,11 +115,25 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
       a.ref = o.xin; a.ref_f32 = 0; a.ldref = h->L[0].Kp;
       a.rowsq = o.rs[0];
       route(a, 0);
+      if (gr) {
+        // d0 where the pass stores it already (the fit's operand), else into
+        // the groups buffer: the kernel and rowsq are the ungrouped pass's
+        if (!a.diff) { a.diff = gr->d0; a.lddiff = h->L[0].Kp; }
+        d0 = a.diff; ldd0 = a.lddiff;
+      }
     }
     RET_IF(launch(dt, a, st));
     if (h->vib && l == h->n_enc - 1)
       RET_IF(mmad_vib_reparam_fwd(dt, B, h->btl, 1, o.y[l], L.Np, nullptr, nullptr, 0, 0, 1, o.zbuf,
                                   h->L[h->n_enc].Kp, nullptr, st));
+  }
+  if (gr) {
+    // all `rows` rows: rows >= B hold d = 0, so score 0 (and flag 0: n_flag)
+    MmadGroupSq q{};
+    q.d = d0; q.ldd = ldd0; q.N = rows; q.n_flag = B; q.G = gr->G;
+    for (int g = 0; g <= gr->G; ++g) q.bounds[g] = gr->bounds[g];
+    q.thr = gr->thr; q.out = gr->out; q.ldo = rows; q.flags = gr->flags; q.ldf = rows;
+    RET_IF(mmad_group_sq_launch(q, st));
   }
   // pass 2: x_hat through the encoder, each layer against its pass-1 output
   const void* cur = o.y[nL - 1];
@@ -139,11 +167,29 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
   return rows == 16 ? mmad_online_finish(fin, st) : mmad_online_finish64(fin, st);
 }
 
-// both entry points; rows = 16 (mmad_ae_online_score) or 64 (_score64)
+int64_t mmad_ae_online_groups_bytes(const mmad_ae* h, int rows) {
+  if (!h || (rows != 16 && rows != 64)) return -1;
+  return ((int64_t)rows * h->L[0].Kp * 4 + 255) / 256 * 256;
+}
+
+// the entry points; rows = 16 (mmad_ae_online_score) or 64 (_score64); gr:
+// the grouped form's arguments, checked here (d0 filled in)
 static int online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
                         const float* thresholds, float* out, uint8_t* flags, void* state,
-                        int64_t state_bytes, int use_graph, void* stream, int rows) {
+                        int64_t state_bytes, int use_graph, void* stream, int rows,
+                        OnlineGroups* gr = nullptr, void* gstate = nullptr, int64_t gstate_bytes = 0) {
   MMAD_CHECK_ARG(h, "ae_online_score: null handle");
+  if (gr) {
+    MMAD_CHECK_ARG(gr->bounds[gr->G] <= h->L[0].K, "ae_online_score_groups: bounds[G]=%d exceeds the "
+                   "input width D=%d", gr->bounds[gr->G], h->L[0].K);
+    MMAD_CHECK_ARG(gr->out, "ae_online_score_groups: null group_out");
+    const int64_t gneed = mmad_ae_online_groups_bytes(h, rows);
+    MMAD_CHECK_ARG(gstate && gstate_bytes >= gneed, "ae_online_score_groups: gstate null or too small "
+                   "(%lld < %lld bytes, mmad_ae_online_groups_bytes)",
+                   (long long)(gstate ? gstate_bytes : 0), (long long)gneed);
+    MMAD_CHECK_ARG(((uintptr_t)gstate) % 256 == 0, "ae_online_score_groups: gstate must be 256-byte aligned");
+    gr->d0 = (float*)gstate;
+  }
   const char* sfx = rows == 16 ? "" : "64";
   MMAD_CHECK_ARG(B >= 1 && B <= rows, "ae_online_score%s: B=%d outside 1..%d (the batch path, "
                  "mmad_ae_score_stream, serves larger calls)", sfx, B, rows);
@@ -175,11 +221,16 @@ static int online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_sta
     h->online_ready = tag;
   }
   auto pass = [&](hipStream_t s) {
-    return online_pass(h, x, ld_x, B, s0, s1, thresholds, out, flags, o, rows, s);
+    return online_pass(h, x, ld_x, B, s0, s1, thresholds, out, flags, o, rows, s, gr);
   };
   if (!use_graph) return pass(st);
   const void* nap_vt = h->nap.on ? (const void*)h->nap.vt : nullptr;
-  const OnlineKey key{x, ld_x, B, s0, s1, thresholds, out, flags, state, weights(h, h->L[0]), nap_vt, rows};
+  OnlineKey key{x, ld_x, B, s0, s1, thresholds, out, flags, state, weights(h, h->L[0]), nap_vt, rows};
+  if (gr) {
+    key.G = gr->G;
+    for (int g = 0; g <= gr->G; ++g) key.bounds[g] = gr->bounds[g];
+    key.gthr = gr->thr; key.gout = gr->out; key.gflags = gr->flags; key.gstate = gstate;
+  }
   if (hipGraphExec_t hit = h->ographs.find(key)) {
     MMAD_HIP_CHECK(hipGraphLaunch(hit, st));
     return MMAD_OK;
@@ -203,4 +254,24 @@ int mmad_ae_online_score64(mmad_ae* h, const float* x, int ld_x, int B, int sap_
                            int64_t state_bytes, int use_graph, void* stream) {
   return online_score(h, x, ld_x, B, sap_start, sap_end, thresholds, out, flags, state, state_bytes,
                       use_graph, stream, 64);
+}
+
+int mmad_ae_online_score_groups(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
+                                const float* thresholds, float* out, uint8_t* flags, void* state,
+                                int64_t state_bytes, int use_graph, void* stream, int rows,
+                                const int* bounds, int G, const float* group_thresholds, float* group_out,
+                                uint8_t* group_flags, void* gstate, int64_t gstate_bytes) {
+  MMAD_CHECK_ARG(rows == 16 || rows == 64, "ae_online_score_groups: rows=%d (16 or 64)", rows);
+  MMAD_CHECK_ARG(G >= 1 && G <= MMAD_MAX_GROUPS, "ae_online_score_groups: G=%d outside 1..%d", G,
+                 MMAD_MAX_GROUPS);
+  MMAD_CHECK_ARG(bounds && bounds[0] >= 0, "ae_online_score_groups: bounds null or bounds[0] negative");
+  OnlineGroups gr{};
+  gr.G = G;
+  for (int g = 0; g <= G; ++g) gr.bounds[g] = bounds[g];
+  for (int g = 0; g < G; ++g)
+    MMAD_CHECK_ARG(bounds[g] < bounds[g + 1], "ae_online_score_groups: bounds not strictly ascending "
+                   "(bounds[%d]=%d, bounds[%d]=%d)", g, bounds[g], g + 1, bounds[g + 1]);
+  gr.thr = group_thresholds; gr.out = group_out; gr.flags = group_flags;
+  return online_score(h, x, ld_x, B, sap_start, sap_end, thresholds, out, flags, state, state_bytes,
+                      use_graph, stream, rows, &gr, gstate, gstate_bytes);
 }

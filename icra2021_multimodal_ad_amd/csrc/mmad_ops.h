@@ -74,6 +74,22 @@ int mmad_online_finish(const MmadOnlineFinish& f, void* stream);
 // the 64-row form: rs [tiles][64], out [n_diff + 3][64], flags [3][64]
 int mmad_online_finish64(const MmadOnlineFinish& f, void* stream);
 
+// ---- column-group mean squares (mmad_group_sq, mmad_group.hip): the bounds
+// travel in the argument struct.  n_flag: rows >= n_flag get flag 0 whatever
+// their score (the online pass's padding rows; the C-ABI form sets it to N)
+struct MmadGroupSq {
+  const float* d;        // [N][ldd] fp32
+  int64_t ldd, N, n_flag;
+  int G;
+  int bounds[MMAD_MAX_GROUPS + 1];
+  const float* thr;      // [G], nullable
+  float* out;            // [G][ldo]
+  int64_t ldo;
+  uint8_t* flags;        // [G][ldf], nullable
+  int64_t ldf;
+};
+int mmad_group_sq_launch(const MmadGroupSq& a, void* stream);
+
 #define MMAD_MAX_REDUCE_JOBS 24
 struct MmadReduceJob {
   const float* src;   // partials, row i at src + i*stride

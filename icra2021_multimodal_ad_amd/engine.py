@@ -536,14 +536,60 @@ class NativeAE:
             raise _native.NativeError("online state size query failed")
         return torch.zeros(need + 256, dtype=torch.uint8, device=self.device)
 
+    def group_sq(self, d, bounds, out=None, thresholds=None, flags=None):
+        """Mean square of the column groups [bounds[g], bounds[g+1]) of d
+        (mmad_group_sq): d fp32 [N, >= bounds[-1]] on this device with unit
+        column stride (any row stride), bounds G + 1 ascending columns.
+        Returns out fp32 [G, N] (given: [>= G, >= N], unit column stride);
+        flags uint8 of the same shape (optional) = out > thresholds[g]
+        (fp32 [G] device tensor; None: flags 0)."""
+        self._require(d)
+        if d.dtype != torch.float32 or d.dim() != 2 or d.stride(1) != 1:
+            raise ValueError("group_sq: d must be fp32 [N, W] with unit column stride")
+        bounds = [int(b) for b in bounds]
+        G, N = len(bounds) - 1, d.shape[0]
+        if out is None:
+            out = torch.empty((max(G, 0), N), device=self.device)
+        for name, t, dt in (("out", out, torch.float32), ("flags", flags, torch.uint8)):
+            if t is not None and (t.device != d.device or t.dtype != dt or t.dim() != 2 or t.stride(1) != 1
+                                  or t.shape[0] < G or t.shape[1] < N):
+                raise ValueError(f"group_sq: {name} must be {dt} [>= G, >= N] with unit column stride")
+        self._check_group_thresholds(thresholds, G, "group_sq")
+        call("mmad_group_sq", N, ptr(d), d.stride(0), (ctypes.c_int * len(bounds))(*bounds), G,
+             ptr(thresholds), ptr(out), out.stride(0), ptr(flags), flags.stride(0) if flags is not None else 0,
+             stream_ptr())
+        return out
+
+    def _check_group_thresholds(self, thresholds, G, what):
+        if thresholds is not None and (thresholds.device != self.device or thresholds.dtype != torch.float32
+                                       or not thresholds.is_contiguous() or thresholds.numel() < G):
+            raise ValueError(f"{what}: group thresholds must be contiguous fp32 [G] on the model device")
+
+    def online_groups_state(self, rows=16):
+        """The second buffer of a grouped online_score call
+        (mmad_ae_online_groups_bytes): uint8 on this device, [rows, Kp0] fp32
+        worth, where the pass leaves d0 when no attached fit stores it."""
+        self._online_sfx(rows)
+        need = int(self._lib.mmad_ae_online_groups_bytes(self._h, int(rows)))
+        if need < 0:
+            raise _native.NativeError("online groups buffer size query failed")
+        return torch.zeros(need + 256, dtype=torch.uint8, device=self.device)
+
     def online_score(self, x, B, out, state, flags=None, thresholds=None, start=0, end=None,
-                     graph=True, rows=16):
+                     graph=True, rows=16, groups=None, group_out=None, group_flags=None,
+                     group_thresholds=None, groups_state=None):
         """Scores of B <= rows windows now (mmad_ae_online_score; rows=64:
         mmad_ae_online_score64): x fp32 [>=B, D] on this device, out fp32
         [n_enc+4, rows] (layer_sq rows, BASE, SAP, NAP), flags uint8 [3, rows]
         and thresholds fp32 [3] optional device tensors, state from
         online_state(rows).  With graph=True a repeated call (the same
-        tensors) replays one captured hipGraph."""
+        tensors) replays one captured hipGraph.
+        groups (None: the call above, untouched): G + 1 ascending input
+        columns; the pass then also writes the per-group mean of d0^2 into
+        group_out fp32 [G, rows] (every column: >= B as 0) and group_flags
+        uint8 [G, rows] (optional) = group_out > group_thresholds[g] (fp32 [G],
+        optional), through mmad_ae_online_score_groups; groups_state from
+        online_groups_state(rows)."""
         sfx = self._online_sfx(rows)
         self._require(x)
         if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or \
@@ -564,9 +610,26 @@ class NativeAE:
         base = state.data_ptr()
         aligned = (base + 255) // 256 * 256
         end = self.n_enc + 2 if end is None else int(end)
-        call("mmad_ae_online_score" + sfx, self._h, ptr(x), x.stride(0), int(B), int(start), end,
+        if groups is None:
+            call("mmad_ae_online_score" + sfx, self._h, ptr(x), x.stride(0), int(B), int(start), end,
+                 ptr(thresholds), ptr(out), ptr(flags), ctypes.c_void_p(aligned),
+                 state.numel() - (aligned - base), 1 if graph else 0, stream_ptr())
+            return out
+        bounds = [int(b) for b in groups]
+        G = len(bounds) - 1
+        for name, t, dt in (("group_out", group_out, torch.float32), ("group_flags", group_flags, torch.uint8)):
+            if t is not None and (t.device != self.device or t.dtype != dt or not t.is_contiguous()
+                                  or tuple(t.shape) != (G, rows)):
+                raise ValueError(f"online_score: {name} must be contiguous {dt} [G, {rows}] on the model device")
+        self._check_group_thresholds(group_thresholds, G, "online_score")
+        gbase = groups_state.data_ptr() if groups_state is not None else 0
+        galigned = (gbase + 255) // 256 * 256
+        call("mmad_ae_online_score_groups", self._h, ptr(x), x.stride(0), int(B), int(start), end,
              ptr(thresholds), ptr(out), ptr(flags), ctypes.c_void_p(aligned),
-             state.numel() - (aligned - base), 1 if graph else 0, stream_ptr())
+             state.numel() - (aligned - base), 1 if graph else 0, stream_ptr(), int(rows),
+             (ctypes.c_int * len(bounds))(*bounds), G, ptr(group_thresholds), ptr(group_out), ptr(group_flags),
+             ctypes.c_void_p(galigned) if groups_state is not None else None,
+             groups_state.numel() - (galigned - gbase) if groups_state is not None else 0)
         return out
 
     def diff_widths(self):

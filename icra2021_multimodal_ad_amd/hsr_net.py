@@ -18,8 +18,27 @@ from . import _native
 
 # modality -> (channels of its 8x8 block, packed row width)
 _BLOCK = {"r": 16, "d": 8, "t": 1, "m": 2}
+# config.sensor of a unimodal module -> its modality
+_SENSOR = {"hand_camera": "r", "head_depth": "d", "force_torque": "t", "mic": "m"}
 # parameters the kernel reads, in the packed order of mmad_hsr_fuse
 _PACKED = ("conv1r", "conv2r", "conv3r", "conv1d", "conv2d", "conv3d", "conv1l", "conv2l")
+
+
+def modality_columns(sensor=None):
+    """The column ranges of HSR_Net.modality_columns: of the fused row
+    (sensor None or 'All'), or of the unimodal row of ``sensor``."""
+    if sensor in (None, "All"):
+        cols, c = {}, 0
+        for k, chans in _BLOCK.items():
+            cols[k] = (c, c + 64 * chans)
+            c += 64 * chans
+        return cols
+    if sensor not in _SENSOR:
+        raise ValueError(f"modality_columns: unknown sensor {sensor!r}")
+    return {_SENSOR[sensor]: (0, 64 * _BLOCK[_SENSOR[sensor]])}
+
+
+FUSED_WIDTH = 64 * sum(_BLOCK.values())
 
 
 class HSR_Net(nn.Module):
@@ -46,6 +65,18 @@ class HSR_Net(nn.Module):
         self.conv1m = nn.Conv1d(1, 12, kernel_size=2, stride=1)
         self.conv2m = nn.Conv1d(12, 8, kernel_size=2, stride=2, padding=2)
         self.unimodal = unimodal
+
+    def modality_columns(self):
+        """Modality -> (first, past-the-last) column of its 8x8 blocks in the
+        flattened output row: the four blocks in torch.cat's order for the
+        fused module, the single block of ``config.sensor`` for a unimodal
+        one (online.OnlineScorer's ``groups``)."""
+        if not self.unimodal:
+            return modality_columns()
+        sensor = getattr(self.config, "sensor", None)
+        if sensor not in _SENSOR:
+            raise ValueError(f"HSR_Net.modality_columns: unimodal module with config.sensor={sensor!r}")
+        return modality_columns(sensor)
 
     def packed_weights(self):
         """fp32 [mmad_hsr_weight_count()] on the module's device (conv1r w, b, ...)."""

@@ -164,9 +164,15 @@ class NoveltyDetecter:
         whole online path runs on the fp32 twin of ``_nap_model`` (NAP needs
         fp32 diffs and one graph is to produce all three scores).  The
         thresholds are calibrated on ``valid_x`` (metric.threshold_metrics'
-        quantile rule on the batch route's validation scores).  Single
+        quantile rule on the batch route's validation scores).
+        ``config.online_groups`` (absent: off) on a model whose input is the
+        fused HSR row: the scorer also returns the per-modality scores of
+        hsr_net.modality_columns(), their thresholds calibrated on the batch
+        route's group scores of ``valid_x`` by the same rule.  Single
         process."""
+        from .hsr_net import FUSED_WIDTH, modality_columns
         from .online import OnlineScorer, rows_for
+        from .reconstruction_aggregation import group_scores
         cfg = self.config
         model.eval()
         start = getattr(cfg, "start_layer_index", 0)
@@ -190,7 +196,14 @@ class NoveltyDetecter:
             lv = _layer_sq(nm, valid_x, 698).t().contiguous().t()
             valid = {"base": base_from_layer_sq(lv, widths), "sap": sap_from_layer_sq(lv, widths, start, end),
                      "nap": nap.score(_device_diffs(nm, valid_x, 698)[:, sel])}
-            scorer = OnlineScorer(nm, nap=nap, start_layer_index=start, end_layer_index=end, rows=rows)
+            groups = None
+            if bool(getattr(cfg, "online_groups", False)) and widths[0] == FUSED_WIDTH:
+                groups = modality_columns()
+            scorer = OnlineScorer(nm, nap=nap, start_layer_index=start, end_layer_index=end, rows=rows,
+                                  groups=groups)
+            if groups is not None:
+                gs = group_scores(torch.as_tensor(valid_x), nm, scorer.groups)
+                valid["groups"] = dict(zip(scorer.group_names, gs))
             scorer.calibrate(valid)
         return scorer
 

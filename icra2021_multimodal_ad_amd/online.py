@@ -11,15 +11,44 @@ default) or 64 (mmad_ae_online_score64: up to four 16-row tiles against one
 weight stream, every window's scores the bits of the 16-row path's).  More
 windows than ``rows`` are the batch route's
 (reconstruction_aggregation.score_windows).
+
+``groups`` adds per-modality scores: the mean squared reconstruction error of
+named column ranges of the input row (HSR_Net.modality_columns() for the fused
+row), from one more launch in the same graph (mmad_ae_online_score_groups).
+The ranges are CONTIGUOUS: each starts where the one before it ends (the
+operator takes ascending bounds); a caller who wants a gap names the gap as a
+group of its own and ignores its row.
 """
 import numpy as np
 import torch
 
 from . import metric
+from ._native import MAX_GROUPS
 
 ROWS = 16            # the default row capacity
 ROW_CAPACITIES = (16, 64)
 METHODS = ("base", "sap", "nap")
+
+
+def group_bounds(groups, width):
+    """(names, bounds) of ``groups``: a mapping name -> (c0, c1) or a list of
+    (c0, c1) pairs (named by position), ordered by c0, contiguous, inside
+    [0, width].  bounds: the G + 1 ascending columns mmad_group_sq takes."""
+    items = list(groups.items()) if hasattr(groups, "items") else list(enumerate(groups))
+    items = sorted(((n, (int(c[0]), int(c[1]))) for n, c in items), key=lambda it: it[1][0])
+    if not 1 <= len(items) <= MAX_GROUPS:
+        raise ValueError(f"OnlineScorer: {len(items)} groups (1..{MAX_GROUPS})")
+    bounds = [items[0][1][0]]
+    for name, (c0, c1) in items:
+        if c0 != bounds[-1]:
+            raise ValueError(f"OnlineScorer: group {name!r} starts at column {c0}, the one before it ends at "
+                             f"{bounds[-1]}: groups are contiguous (name a gap as a group of its own)")
+        if c1 <= c0:
+            raise ValueError(f"OnlineScorer: group {name!r} is empty ({c0}, {c1})")
+        bounds.append(c1)
+    if bounds[0] < 0 or bounds[-1] > width:
+        raise ValueError(f"OnlineScorer: groups span [{bounds[0]}, {bounds[-1]}) outside the {width} input columns")
+    return tuple(n for n, _ in items), bounds
 
 
 def rows_for(n_windows):
@@ -32,8 +61,12 @@ def rows_for(n_windows):
 
 
 class OnlineScorer:
+    # per-modality scores: off unless ``groups`` is given (then instance attributes)
+    groups = None
+    group_names = ()
+
     def __init__(self, model, nap=None, start_layer_index=0, end_layer_index=None, thresholds=None,
-                 rows=ROWS):
+                 rows=ROWS, groups=None):
         """model: an eval-mode autoencoder of the plugin surface (fp32 or bf16,
         no split-bf16 score planes).  nap: a fitted NapScorer (its fit is
         attached to ``model`` for this object's lifetime; a standalone scorer
@@ -41,7 +74,11 @@ class OnlineScorer:
         start / end_layer_index: the SAP layer range as
         ``sap_from_layer_sq`` takes it.  thresholds: {'base','sap','nap'} ->
         float, or None (NaN: no flag until ``calibrate``).  rows: 16 or 64,
-        the most windows a call takes (the size of every buffer here)."""
+        the most windows a call takes (the size of every buffer here).
+        groups: None, or named column ranges of the input row (a mapping name
+        -> (c0, c1) or a list of pairs; contiguous, see the module text):
+        ``score`` then also returns their mean squared reconstruction error
+        and flags against thresholds['groups'] (name -> float)."""
         if rows not in ROW_CAPACITIES:
             raise ValueError(f"OnlineScorer: rows={rows!r} (16 or 64)")
         self.rows = rows
@@ -64,43 +101,73 @@ class OnlineScorer:
         self.flags = torch.zeros((3, rows), device=dev, dtype=torch.uint8)
         self.thresholds = torch.full((3,), float("nan"), device=dev)
         self.state = nat.online_state(rows)
+        if groups is not None:
+            self.group_names, self.groups = group_bounds(groups, nat.enc_widths[0])
+            G = len(self.group_names)
+            self.group_out = torch.zeros((G, rows), device=dev)
+            self.group_flags = torch.zeros((G, rows), device=dev, dtype=torch.uint8)
+            self.group_thresholds = torch.full((G,), float("nan"), device=dev)
+            self.groups_state = nat.online_groups_state(rows)
         if thresholds is not None:
             self.set_thresholds(thresholds)
 
     def set_thresholds(self, thresholds):
         """{'base','sap','nap'} -> float (a missing one: NaN, no flag), written
-        into the device buffer the pass reads: the next replay sees them."""
+        into the device buffer the pass reads: the next replay sees them.
+        With groups, 'groups' -> {name: float} sets the group thresholds the
+        same way (a missing name: NaN; no 'groups' entry: left as they are)."""
         t = torch.tensor([float(thresholds.get(k, float("nan"))) for k in METHODS], dtype=torch.float32)
         self.thresholds.copy_(t)
+        gt = thresholds.get("groups")
+        if gt is not None:
+            if self.groups is None:
+                raise ValueError("OnlineScorer: thresholds['groups'] on a scorer without groups")
+            self.group_thresholds.copy_(torch.tensor([float(gt.get(n, float("nan"))) for n in self.group_names],
+                                                     dtype=torch.float32))
         return t
 
     def calibrate(self, valid_scores, q=metric.F1_QUANTILE):
         """Thresholds by the quantile rule of metric.threshold_metrics
         (np.quantile(valid, q), linear) on validation scores {'base','sap','nap'}
-        -> [Nv]; returns them as a dict."""
+        -> [Nv]; returns them as a dict.  With groups, 'groups' -> {name:
+        [Nv]} calibrates each named group's threshold by the same rule."""
+        def quantile(v):
+            v = torch.as_tensor(v).reshape(-1)
+            return metric.threshold_metrics(v, v[:1], np.zeros(1, np.uint8), q)[0]
         thr = {}
         for k in METHODS:
             v = valid_scores.get(k)
             if v is not None:
-                v = torch.as_tensor(v).reshape(-1)
-                thr[k] = metric.threshold_metrics(v, v[:1], np.zeros(1, np.uint8), q)[0]
+                thr[k] = quantile(v)
+        gv = valid_scores.get("groups")
+        if gv is not None:
+            thr["groups"] = {n: quantile(v) for n, v in gv.items() if v is not None}
         self.set_thresholds(thr)
         return thr
 
     def _run(self, B):
         n_enc = self.nat.n_enc
+        grouped = {} if self.groups is None else dict(
+            groups=self.groups, group_out=self.group_out, group_flags=self.group_flags,
+            group_thresholds=self.group_thresholds, groups_state=self.groups_state)
         self.nat.online_score(self.x, B, self.out, self.state, flags=self.flags,
                               thresholds=self.thresholds, start=self.start, end=self.end,
-                              rows=self.rows)
-        return {"layer_sq": self.out[:n_enc + 1, :B], "base": self.out[n_enc + 1, :B],
-                "sap": self.out[n_enc + 2, :B],
-                "nap": self.out[n_enc + 3, :B] if self.nap is not None else None,
-                "flags": self.flags[:, :B]}
+                              rows=self.rows, **grouped)
+        res = {"layer_sq": self.out[:n_enc + 1, :B], "base": self.out[n_enc + 1, :B],
+               "sap": self.out[n_enc + 2, :B],
+               "nap": self.out[n_enc + 3, :B] if self.nap is not None else None,
+               "flags": self.flags[:, :B]}
+        if self.groups is not None:
+            res["groups"] = self.group_out[:, :B]
+            res["group_flags"] = self.group_flags[:, :B]
+        return res
 
     def score(self, x):
         """x: [B <= rows, D], host or device.  Returns {'base','sap','nap',
         'layer_sq','flags'}: views of this object's fixed outputs on the
-        device, rewritten by the next call (copy what you keep)."""
+        device, rewritten by the next call (copy what you keep).  With groups
+        also 'groups' [G, B] and 'group_flags' [G, B], rows in the order of
+        ``group_names`` (ascending columns)."""
         x = torch.as_tensor(x)
         x = x.reshape(x.shape[0], -1)
         B = x.shape[0]

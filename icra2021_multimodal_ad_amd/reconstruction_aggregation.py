@@ -65,6 +65,33 @@ def score_windows(x, model, batch_size=65536, out=None, graph=True, nap=None, na
     return out if nap is None else (out, nap_out)
 
 
+def group_scores(x, model, groups, batch_size=65536):
+    """Per-modality scores on the batch route: [G, N] fp32 on the device, the
+    mean of d0^2 = (x_hat - x)^2 over each column group.  groups: G + 1
+    ascending input columns (mmad_group_sq's bounds), or named ranges as
+    online.OnlineScorer takes them (rows then in ascending column order).
+    Per batch: the materialised diffs of ``score(xb, want_diffs=True)``, then
+    mmad_group_sq over their columns [0, D) -- the same operator, hence the
+    same bits per window, as the online pass."""
+    from .online import group_bounds
+    model.eval()
+    nat = model._native
+    dev = _device_of(model)
+    if hasattr(groups, "items") or (len(groups) and not np.isscalar(groups[0])):
+        groups = group_bounds(groups, nat.enc_widths[0])[1]
+    bounds = [int(b) for b in groups]
+    if not bounds or bounds[-1] > nat.enc_widths[0]:
+        raise ValueError(f"group_scores: bounds {bounds} outside the {nat.enc_widths[0]} input columns")
+    n = x.shape[0]
+    out = torch.empty((len(bounds) - 1, n), device=dev)
+    with torch.no_grad():
+        for s in range(0, n, batch_size):
+            xb = x[s:s + batch_size].to(dev, non_blocking=True).float().reshape(-1, nat.enc_widths[0])
+            _, diffs = nat.score(xb, want_diffs=True)
+            nat.group_sq(diffs, bounds, out=out[:, s:s + xb.shape[0]])
+    return out
+
+
 def base_from_layer_sq(layer_sq, widths):
     """utils/metric.py:133: mean_d(d0^2)."""
     return layer_sq[0] / float(widths[0])

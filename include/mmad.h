@@ -232,6 +232,30 @@ int mmad_fc_rows64(int dtype, int M, int N, int K, int Np, int Kp, const void* x
                    const float* bn_shift, void* y, const void* ref, int ref_dtype, int ldref,
                    float* diff, int lddiff, const float* colw, float* rowsq, void* stream);
 
+/* Mean square of column groups of an fp32 matrix: the per-modality anomaly
+ * scores (no reference counterpart).  bounds: HOST array of G + 1 strictly
+ * ascending columns, 0 <= bounds[0], bounds[G] <= ldd, 1 <= G <=
+ * MMAD_MAX_GROUPS; group g is the columns [bounds[g], bounds[g + 1]) -- any
+ * boundaries, contiguous by construction (a caller who wants a gap names it
+ * as a group and ignores its row).
+ *   out[g][n]   = sum_c d[n][c]^2 / (bounds[g + 1] - bounds[g])     n < N
+ *   flags[g][n] = out[g][n] > thresholds[g]
+ * d fp32 [N][ldd] (device, 4-byte aligned; rows whose base is 16-byte aligned
+ * are read with 16-byte loads); out fp32 [G][ld_out], flags (nullable) uint8
+ * [G][ld_flags], thresholds (nullable: every flag 0) fp32 [G] in device
+ * memory; strict >, so a NaN threshold flags nothing.  Columns >= N of out and
+ * flags are not written.  The summation order of one (row, group) depends on
+ * the group's two bounds alone (lane-strided accumulation over aligned column
+ * quads, then a fixed shuffle tree; no atomics): a row's result is the same
+ * bits whatever N, ldd, the row's position or the other groups are.
+ * MMAD_EINVAL, nothing launched: G outside 1..MMAD_MAX_GROUPS, bounds null,
+ * negative, not strictly ascending or past ldd, N < 1, a null d or out, a
+ * leading dimension of out / flags below N. */
+#define MMAD_MAX_GROUPS 8
+int mmad_group_sq(int64_t N, const float* d, int64_t ldd, const int* bounds, int G,
+                  const float* thresholds, float* out, int64_t ld_out, uint8_t* flags,
+                  int64_t ld_flags, void* stream);
+
 /* BatchNorm1d eval affine (layers/fc_layer.py:33): scale = gamma/sqrt(rv+eps),
  * shift = beta - rm*scale, for N columns (padded columns -> 0). */
 int mmad_bn_eval_affine(int N, int Np, const float* gamma, const float* beta, const float* rm,
@@ -801,6 +825,38 @@ int64_t mmad_ae_online_state_bytes64(const mmad_ae* h);
 int mmad_ae_online_score64(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
                            const float* thresholds, float* out, uint8_t* flags, void* state,
                            int64_t state_bytes, int use_graph, void* stream);
+
+/* The online pass with per-modality scores: mmad_ae_online_score (rows = 16)
+ * or mmad_ae_online_score64 (rows = 64) -- the same launches on the same
+ * state, the same out and flags to the bit -- plus ONE more launch,
+ * mmad_group_sq on d0 = x_hat - x, the fp32 diffs the decoder's last launch
+ * forms.  bounds / G as mmad_group_sq takes them, over the input columns
+ * (bounds[G] <= D).  group_out fp32 [G][rows]: the mean of d0^2 over each
+ * group's columns; group_flags (nullable) uint8 [G][rows] = group_out >
+ * group_thresholds[g] (fp32 [G], device, read when the pass runs; nullable:
+ * flags 0).  Unlike out, ALL `rows` columns are written: columns >= B as score
+ * 0 and flag 0.  Window i's group scores are the same bits alone, in a 16-row
+ * pass, in a 64-row pass, and from mmad_group_sq over a batch holding the same
+ * d0 row.
+ * d0 is read where the pass already stores it (the NAP operand, when the
+ * attached fit's range starts at diff layer 0); otherwise the last launch's
+ * diff output points at gstate, a second caller-owned, 256-byte aligned device
+ * buffer of mmad_ae_online_groups_bytes(h, rows) bytes ([rows][Kp0] fp32; -1
+ * for a null handle or rows other than 16 / 64), always required.
+ * A grouped pass has its own graph signature (the group buffers, G and the
+ * bounds' values are part of it) in the handle's 8 online graphs: grouped and
+ * ungrouped callers may take turns on one handle.
+ * MMAD_EINVAL, nothing launched: rows other than 16 / 64, G outside
+ * 1..MMAD_MAX_GROUPS, bounds null / not strictly ascending / bounds[G] > D, a
+ * null group_out, gstate null, too small or misaligned, and every refusal of
+ * mmad_ae_online_score. */
+int64_t mmad_ae_online_groups_bytes(const mmad_ae* h, int rows);
+int mmad_ae_online_score_groups(mmad_ae* h, const float* x, int ld_x, int B, int sap_start,
+                                int sap_end, const float* thresholds, float* out, uint8_t* flags,
+                                void* state, int64_t state_bytes, int use_graph, void* stream,
+                                int rows, const int* bounds, int G, const float* group_thresholds,
+                                float* group_out, uint8_t* group_flags, void* gstate,
+                                int64_t gstate_bytes);
 
 /* Split-K health of the executor workspace `ws` (as mmad_gemm_status): a
  * no-op returning MMAD_OK unless split-K is enabled (tuning knob 4 > 1);

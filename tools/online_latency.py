@@ -27,7 +27,14 @@ once (AE weights + the encoder again + V^T) / 8 TB/s.
         (c16) mmad_ae_online_score, replayed, where B <= 16
         (c64) mmad_ae_online_score64, replayed
       and the two comparisons the documents rest on: c64 / b at every B, c64 /
-      c16 at B <= 16 (a route is the faster one beyond the 3 % spread)."""
+      c16 at B <= 16 (a route is the faster one beyond the 3 % spread).
+  python tools/online_latency.py --groups [--out profiles/online_groups_latency.json]
+      per-modality scores (mmad_ae_online_score_groups): the grouped and the
+      ungrouped pass alternated in one process at B = 10, 16 (16 rows) and 64
+      (64 rows), both handles, with the fit (d0 read from the NAP operand) and
+      without (d0 into the groups buffer); groups = the fused row's modality
+      columns scaled to the model's D.  The grouped pass is one dependent
+      launch more; a difference inside the 3 % spread decides nothing."""
 import argparse
 import ctypes
 import json
@@ -211,6 +218,76 @@ def run_rows64(dtype):
     return cases
 
 
+GROUPS_B = (10, 16, 64)
+FUSED_BOUNDS = (0, 1024, 1536, 1600, 1728)
+
+
+def run_groups(dtype):
+    lib = _native.load()
+    m = build(dtype)
+    nat = m._native
+    h, s = nat._h, stream_ptr()
+    D, n = nat.enc_widths[0], nat.n_enc
+    bounds = [round(c * D / FUSED_BOUNDS[-1]) for c in FUSED_BOUNDS]
+    G = len(bounds) - 1
+    cb = (ctypes.c_int * len(bounds))(*bounds)
+    x = torch.randn((64, D), device="cuda")
+    thr, gthr = torch.ones(3, device="cuda"), torch.ones(G, device="cuda")
+    nat.sync_shadow()
+    cases = {}
+    for with_nap in (False, True):
+        if with_nap:
+            fit = random_fit(nat)
+            nat.set_nap(fit)
+        for B in GROUPS_B:
+            rows = 16 if B <= 16 else 64
+            # each pass its own outputs and state: neither replays into the other's buffers
+            bufs = {}
+            for tag in ("plain", "grouped"):
+                state = nat.online_state(rows)
+                al = (state.data_ptr() + 255) // 256 * 256
+                bufs[tag] = (torch.zeros((n + 4, rows), device="cuda"),
+                             torch.zeros((3, rows), device="cuda", dtype=torch.uint8), state,
+                             (ctypes.c_void_p(al), state.numel() - (al - state.data_ptr())))
+            gstate = nat.online_groups_state(rows)
+            gal = (gstate.data_ptr() + 255) // 256 * 256
+            gout = torch.zeros((G, rows), device="cuda")
+            gflags = torch.zeros((G, rows), device="cuda", dtype=torch.uint8)
+            o, f, _, (sp, sb) = bufs["plain"]
+            p_fn = getattr(lib, "mmad_ae_online_score" + ("" if rows == 16 else "64"))
+            p_args = (h, ptr(x), D, B, 0, n + 2, ptr(thr), ptr(o), ptr(f), sp, sb, 1, s)
+            o2, f2, _, (sp2, sb2) = bufs["grouped"]
+            g_args = (h, ptr(x), D, B, 0, n + 2, ptr(thr), ptr(o2), ptr(f2), sp2, sb2, 1, s, rows, cb, G,
+                      ptr(gthr), ptr(gout), ptr(gflags), ctypes.c_void_p(gal),
+                      gstate.numel() - (gal - gstate.data_ptr()))
+            res = measure({"ungrouped": lambda: _native.check(p_fn(*p_args), "ungrouped"),
+                           "grouped": lambda: _native.check(lib.mmad_ae_online_score_groups(*g_args), "grouped")})
+            assert torch.equal(o[:n + 3, :B], o2[:n + 3, :B]) and torch.isfinite(gout).all()
+            assert (gout[:, :B] > 0).all() and (gout[:, B:] == 0).all()
+            med = {k: v["gpu"]["median_us"] for k, v in res.items()}
+            res["grouped_minus_ungrouped_gpu_us"] = med["grouped"] - med["ungrouped"]
+            res["grouped_vs_ungrouped_gpu"] = med["grouped"] / med["ungrouped"]
+            res["rows"] = rows
+            cases[f"{dtype}_{'nap' if with_nap else 'nonap'}_B{B}"] = res
+            print(f"{dtype} nap={int(with_nap)} B={B}", {k: round(v, 1) for k, v in med.items()}, flush=True)
+    nat.set_nap(None)
+    return bounds, cases
+
+
+def main_groups(out):
+    cases = {}
+    for dt in ("f32", "bf16"):
+        bounds, c = run_groups(dt)
+        cases.update(c)
+    doc = {"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "calls": CALLS, "spread": SPREAD,
+           "bounds": bounds, "cases": cases,
+           "outside_spread": {k: c["grouped_vs_ungrouped_gpu"] for k, c in cases.items()
+                              if abs(c["grouped_vs_ungrouped_gpu"] - 1) > SPREAD}}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+
+
 def main_rows64(out):
     cases = {}
     for dt in ("f32", "bf16"):
@@ -235,10 +312,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--variant", default=None)
     ap.add_argument("--rows64", action="store_true")
+    ap.add_argument("--groups", action="store_true")
     a = ap.parse_args()
     _native.require_gpu()
     if a.rows64:
         return main_rows64(a.out or "profiles/online_rows64_latency.json")
+    if a.groups:
+        return main_groups(a.out or "profiles/online_groups_latency.json")
     a.out = a.out or "profiles/online_latency.json"
     cases = {f"{dt}_B{B}": run_case(dt, B, a.variant) for dt in ("f32", "bf16") for B in (10, 16)}
     if a.variant:
