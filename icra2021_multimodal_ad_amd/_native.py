@@ -17,6 +17,7 @@ F32, BF16 = 0, 1
 BF16X3 = 2   # split-bf16 planes: eval / score path only (include/mmad.h)
 ACT = {None: 0, "leakyrelu": 1, "relu": 2, "sigmoid": 3, "tanh": 4}
 MAX_GROUPS = 8   # MMAD_MAX_GROUPS: column groups of one mmad_group_sq call
+PCM_I16, PCM_F32 = 0, 1   # MMAD_PCM_*: sample types of mmad_mfcc
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -155,6 +156,12 @@ SIGNATURES = {
     "mmad_threshold_metrics": (_I, [_I64, _P, _I64, _P, _P, ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
     "mmad_hsr_weight_count": (_I, []),
     "mmad_hsr_fuse": (_I, [_I, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "mmad_mfcc_frames": (_I64, [_I64, _I]),
+    "mmad_mfcc_filterbank": (_I, [_I, _I, _I, _P]),
+    "mmad_mfcc_plan_bytes": (_I64, [_I, _I, _I, _I]),
+    "mmad_mfcc_plan_init": (_I, [_P, _I64, _I, _I, _I, _I, _P]),
+    "mmad_mfcc_ws_bytes": (_I64, [_I64, _I]),
+    "mmad_mfcc": (_I, [_P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _I64, _F, _F, _P, _P, _I64, _P]),
 }
 
 

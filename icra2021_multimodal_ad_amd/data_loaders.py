@@ -273,3 +273,76 @@ def get_loaders(config, use_full_class=False, device=None, rank=0, world=1):
     train, valid, test = dset_manager.get_loaders(batch_size=config.batch_size,
                                                   indexes_list=indexes_list, rank=rank, world=world)
     return dset_manager, train, valid, test
+
+
+# ---- the deployment loop's input stage (utils/data_loaders.py:676-737) -------
+_front_ends = {}
+
+
+def mic_front_end(window_size=0.1, stride=0.1, device=None):
+    """The 44.1 kHz / 128 mel / 13 coefficient MfccFrontEnd of
+    save_mfcc_from_wav for (window_size, stride) on ``device``, built once."""
+    from .mfcc import MfccFrontEnd, n_fft_of
+    n_fft_of(44100, window_size, stride)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    key = (window_size, stride, dev)
+    if key not in _front_ends:
+        _front_ends[key] = MfccFrontEnd(44100, window_size, stride, device=dev)
+    return _front_ends[key]
+
+
+def save_mfcc_from_wav(mic_q, config, length, window_size=0.1, stride=0.1):
+    """utils/data_loaders.py:676-701: the MFCCs of the raw int16 chunks
+    ``mic_q``, numpy [config.batch_size, 13] (``length`` only feeds the
+    reference's too-short message; the buffer is not cut, :688)."""
+    fe = mic_front_end(window_size, stride, _config_device(config))
+    return fe.latest(mic_q, int(config.batch_size))[0].cpu().numpy()
+
+
+def norm_vec(v, range_in=None, range_out=None):
+    """utils/data_loaders.py:703-712."""
+    if range_out is None:
+        range_out = [-1, 1]
+    if range_in is None:
+        range_in = [torch.min(v), torch.max(v)]
+    r_out = range_out[1] - range_out[0]
+    r_in = range_in[1] - range_in[0]
+    return (r_out * (v - range_in[0]) / r_in) + range_out[0]
+
+
+def normalised_sensors(force_q, hand_q, depth_q, device):
+    """HsrDataset's r, d, t (:715-722) on ``device``: the queues as fp32
+    [n, 1, 3, 32, 32], [n, 1, 1, 32, 32] and [n], norm_vec from [0, 255]
+    (images) and [0, 400] (force/torque) to [-1, 1]."""
+    def dev(q):
+        q = q if torch.is_tensor(q) else torch.from_numpy(np.asarray(q, dtype=np.float32))
+        return q.to(device=device, dtype=torch.float32)
+    r = norm_vec(dev(hand_q).view(-1, 1, 3, 32, 32), range_in=[0, 255])
+    d = norm_vec(dev(depth_q).view(-1, 1, 1, 32, 32), range_in=[0, 255])
+    t = norm_vec(dev(force_q), range_in=[0, 400])
+    return r, d, t
+
+
+def _config_device(config):
+    return torch.device("cuda", max(int(getattr(config, "gpu_id", 0)), 0))
+
+
+def get_realtime_dataloader(config, force_q, hand_q, depth_q, mic_q, hsr_net=None):
+    """utils/data_loaders.py:734-737: one tick's fused rows [batch_size, 1728]
+    from the raw queues.  mic_q is raw PCM (MfccFrontEnd.latest: MFCCs and
+    their norm_vec in one native call).  The reference builds a fresh random
+    conv module every tick (:724); here the caller passes its HSR_Net, and
+    one is built (torch's default init, as the reference's) only without."""
+    import types
+
+    from .hsr_net import HSR_Net
+    B = int(config.batch_size)
+    dev = _config_device(config)
+    if hsr_net is None:
+        hsr_net = HSR_Net(False, types.SimpleNamespace(slicing_size=B, gpu_id=dev.index)).to(dev)
+    if int(hsr_net.batch_size) != B:
+        raise ValueError(f"get_realtime_dataloader: config.batch_size {B} != the module's slicing_size "
+                         f"{hsr_net.batch_size}")
+    r, d, t = normalised_sensors(force_q, hand_q, depth_q, dev)
+    m = mic_front_end(device=dev).latest(mic_q, B)[1]
+    return hsr_net.forward(r, d, None, t, m).reshape(B, -1)

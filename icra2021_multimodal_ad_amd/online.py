@@ -64,6 +64,7 @@ class OnlineScorer:
     # per-modality scores: off unless ``groups`` is given (then instance attributes)
     groups = None
     group_names = ()
+    front_end = None     # score_sensors' MfccFrontEnd (set one to change its settings)
 
     def __init__(self, model, nap=None, start_layer_index=0, end_layer_index=None, thresholds=None,
                  rows=ROWS, groups=None):
@@ -191,6 +192,23 @@ class OnlineScorer:
         if fused.reshape(B, -1).shape[1] != self.x.shape[1]:
             raise ValueError("OnlineScorer.score_frames: the fused row width is not the model's input size")
         return self._run(B)
+
+    def score_sensors(self, hsr_net, force_q, hand_q, depth_q, mic_pcm):
+        """One tick of the deployment loop from the raw queues
+        (get_realtime_dataloader, utils/data_loaders.py:734-737): norm_vec's
+        fixed-range maps of the camera, depth and force/torque frames
+        (elementwise torch), the microphone's MFCCs and their norm_vec to
+        [-1, 1] over the last ``hsr_net.batch_size`` frames (mmad_mfcc, on the
+        same stream, ahead of the replayed graph), then ``score_frames``.
+        mic_pcm: what MfccFrontEnd takes (``self.front_end``: built on first
+        use with the reference's 44.1 kHz / 0.1 s / 128 mel / 13 settings)."""
+        from .data_loaders import mic_front_end, normalised_sensors
+        dev = self.x.device
+        if self.front_end is None:
+            self.front_end = mic_front_end(device=dev)
+        r, d, t = normalised_sensors(force_q, hand_q, depth_q, dev)
+        m = self.front_end.latest(mic_pcm, int(hsr_net.batch_size))[1]
+        return self.score_frames(hsr_net, r, d, t, m)
 
     def close(self):
         """Detach the fit from the model."""

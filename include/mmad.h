@@ -950,6 +950,65 @@ size_t mmad_minmax_norm_ws_bytes(int64_t n, int F);
 int mmad_minmax_norm(int64_t n, int F, const void* v, int vtype, int layout, float* out, void* ws,
                      size_t ws_bytes, void* stream);
 
+/* Microphone front end: MFCCs from raw PCM (save_mfcc_from_wav,
+ * utils/data_loaders.py:676-701, the same recipe as concatdata_maker.py:15-49)
+ * and norm_vec (:703-712) of the latest frames, the stage of
+ * get_realtime_dataloader (:734-737) ahead of mmad_hsr_fuse.  The arithmetic
+ * is librosa 0.8's: melspectrogram(y, sr, n_fft, hop_length = n_fft, n_mels)
+ * -- frame t covers samples t*n_fft - n_fft/2 .. + n_fft - 1 of y, both ends
+ * reflect-padded (-i -> i, L-1+i -> L-1-i), times the periodic Hann window,
+ * power |X_k|^2 of bins 0..n_fft/2, S = mel filterbank . power --
+ * power_to_db(S, ref=np.max): dB = 10 log10(max(1e-10, S)) - 10 log10(max(1e-10,
+ * max S)), floored at max(dB) - 80, both maxima over EVERY frame and mel of
+ * the call (a window's MFCCs depend on the buffer it came in, as in the
+ * reference) -- and mfcc = DCT-II ortho(dB)[:n_mfcc].  Everything after the
+ * PCM load is fp64; the stores are fp32.
+ * Parameters: sr (Hz), n_fft 16..4410 (= the hop: the reference always calls
+ * with window_size == stride; 4410 is the deployment's 0.1 s at 44.1 kHz, 2205
+ * the ETL's after librosa.load resamples to 22050), n_mels 1..128, n_mfcc
+ * 1..n_mels.
+ * mmad_mfcc_frames: librosa's centred frame count 1 + (L + 2*(n_fft/2) -
+ * n_fft) / n_fft of L samples; -1 when L < n_fft/2 + 1 (no reflection exists).
+ * mmad_mfcc_filterbank: HOST function, no GPU: librosa.filters.mel(sr, n_fft,
+ * n_mels, fmin=0, fmax=sr/2, htk=False, norm='slaney') in double -- Slaney mel
+ * scale (linear below 1 kHz, log above, logstep = ln(6.4)/27), triangles from
+ * the ramps, each filter times 2 / (f[i+2] - f[i]) -- dense into the host
+ * array fb [n_mels][n_fft/2+1].
+ * mmad_mfcc_plan_bytes / mmad_mfcc_plan_init: the plan is a caller-owned,
+ * 256-byte aligned device buffer (as the online state is) that the host
+ * fills once, in double, with the periodic Hann window 0.5 - 0.5 cos(2 pi
+ * n/N), the twiddle table cos/sin(2 pi j/N), j = 0..N-1, the filterbank's
+ * nonzero runs and the DCT basis rows 0..n_mfcc-1, and copies over on
+ * `stream` (the call returns when the copy has read its host staging; it is
+ * not capturable).  No library-global state: the plan's header names its
+ * parameters and the kernels write nothing when a call's differ.  plan_bytes
+ * returns -1 for parameters out of range.
+ * mmad_mfcc_ws_bytes: the caller-owned, 256-byte aligned scratch of a call
+ * with n_frames frames: the power spectra (rows of 4410/2 + 1 bins whatever
+ * n_fft is), the mel power [n_frames][n_mels], the per-frame maxima and the
+ * fp64 coefficients; -1 for arguments out of range.
+ * mmad_mfcc: pcm: DEVICE [L] of pcm_type MMAD_PCM_I16 (cast to float without
+ * scaling, as the reference does) or MMAD_PCM_F32.  out: fp32 [n_frames][n_mfcc],
+ * every frame.  norm_out: nullable fp32 [keep][n_mfcc], 1 <= keep <= n_frames:
+ * norm_vec of the LAST keep frames, (hi - lo) (v - min) / (max - min) + lo with
+ * min and max over all keep*n_mfcc values (max == min: what IEEE division
+ * gives, the reference's own result).  Three launches on `stream`, no host
+ * synchronisation (capturable), no atomics, fixed reduction order: a call's
+ * bits repeat.  Returns MMAD_EINVAL and launches nothing for parameters out
+ * of range, a null pcm / plan / out / ws, a plan or workspace too small or
+ * misaligned, L too short, keep out of range or an unknown pcm_type. */
+#define MMAD_PCM_I16 0
+#define MMAD_PCM_F32 1
+int64_t mmad_mfcc_frames(int64_t L, int n_fft);
+int mmad_mfcc_filterbank(int sr, int n_fft, int n_mels, double* fb);
+int64_t mmad_mfcc_plan_bytes(int sr, int n_fft, int n_mels, int n_mfcc);
+int mmad_mfcc_plan_init(void* plan, int64_t bytes, int sr, int n_fft, int n_mels, int n_mfcc,
+                        void* stream);
+int64_t mmad_mfcc_ws_bytes(int64_t n_frames, int n_mels);
+int mmad_mfcc(const void* pcm, int pcm_type, int64_t L, int sr, int n_fft, int n_mels, int n_mfcc,
+              const void* plan, int64_t plan_bytes, float* out, int64_t keep, float lo, float hi,
+              float* norm_out, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
