@@ -3,8 +3,8 @@
 // (mmad_ae_score.hip) pads such a call to 128 rows and spends its ~30 launches
 // on zeros; here every layer is one launch that reads its weights once.  All
 // buffers live in a caller-owned state, carved below for `rows` = 16 or 64: the
-// two entry points share the carve and the launch list and differ in the row
-// capacity of every buffer and in the two kernels behind it.
+// two entry points share the carve, the launch list and the kernels and differ
+// in the row capacity of every buffer.
 #include "mmad_ae_impl.h"
 
 using namespace mmad_ae_impl;
@@ -48,19 +48,15 @@ static void online_carve(const mmad_ae* h, char* base, OnlineWS& o, int rows) {
   o.bytes = (off + 255) / 256 * 256;
 }
 
-int64_t mmad_ae_online_state_bytes(const mmad_ae* h) {
+static int64_t online_state_bytes(const mmad_ae* h, int rows) {
   if (!h) return -1;
   OnlineWS o;
-  online_carve(h, nullptr, o, 16);
+  online_carve(h, nullptr, o, rows);
   return o.bytes;
 }
 
-int64_t mmad_ae_online_state_bytes64(const mmad_ae* h) {
-  if (!h) return -1;
-  OnlineWS o;
-  online_carve(h, nullptr, o, 64);
-  return o.bytes;
-}
+int64_t mmad_ae_online_state_bytes(const mmad_ae* h) { return online_state_bytes(h, 16); }
+int64_t mmad_ae_online_state_bytes64(const mmad_ae* h) { return online_state_bytes(h, 64); }
 
 // per-modality scores of a grouped pass (mmad_ae_online_score_groups)
 struct OnlineGroups {
@@ -78,7 +74,6 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
                        float* out, uint8_t* flags, const OnlineWS& o, int rows, hipStream_t st,
                        const OnlineGroups* gr = nullptr) {
   const int dt = h->dtype;
-  const auto launch = rows == 16 ? mmad_skinny_launch : mmad_skinny_rows_launch;
   const int nL = (int)h->L.size();
   const mmad_ae::NapFit& nf = h->nap;
   RET_IF(mmad_pack_input(dt, B, h->L[0].K, rows, h->L[0].Kp, x, ld_x, o.xin, st));
@@ -98,7 +93,7 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
   };
   auto layer = [&](const AeLayer& L, const void* in, void* y) {
     MmadSkinny a{};
-    a.M = B; a.N = L.N; a.Np = L.Np; a.Kp = L.Kp;
+    a.rows = rows; a.M = B; a.N = L.N; a.Np = L.Np; a.Kp = L.Kp;
     a.x = in; a.w = weights(h, L); a.bias = h->params + L.b_off; a.act = L.act; a.slope = h->slope;
     if (L.bn) { a.scale = o.scale + L.bn_off; a.shift = o.shift + L.bn_off; }
     a.y = y;
@@ -122,7 +117,7 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
         d0 = a.diff; ldd0 = a.lddiff;
       }
     }
-    RET_IF(launch(dt, a, st));
+    RET_IF(mmad_skinny_launch(dt, a, st));
     if (h->vib && l == h->n_enc - 1)
       RET_IF(mmad_vib_reparam_fwd(dt, B, h->btl, 1, o.y[l], L.Np, nullptr, nullptr, 0, 0, 1, o.zbuf,
                                   h->L[h->n_enc].Kp, nullptr, st));
@@ -143,17 +138,17 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
     a.ref = o.y[e]; a.ref_f32 = 0; a.ldref = L.Np;
     a.rowsq = o.rs[e + 1];
     route(a, e + 1);
-    RET_IF(launch(dt, a, st));
+    RET_IF(mmad_skinny_launch(dt, a, st));
     cur = o.p2[e];
   }
   // the NAP run: the same kernel on the fit's fp32 V^T (K = W, N = R), bias
   // after the product, colw = 1 / var, no reference
   if (nf.on) {
     MmadSkinny a{};
-    a.M = B; a.N = nf.R; a.Np = nf.Rp; a.Kp = nf.Kp;
+    a.rows = rows; a.M = B; a.N = nf.R; a.Np = nf.Rp; a.Kp = nf.Kp;
     a.x = o.nap_x; a.w = nf.vt; a.bias = nf.bias; a.act = MMAD_ACT_NONE;
     a.colw = nf.w; a.rowsq = o.nap_rs;
-    RET_IF(launch(MMAD_F32, a, st));
+    RET_IF(mmad_skinny_launch(MMAD_F32, a, st));
   }
   MmadOnlineFinish fin{};
   fin.B = B; fin.n_diff = h->n_enc + 1;
@@ -164,7 +159,7 @@ static int online_pass(mmad_ae* h, const float* x, int ld_x, int B, int s0, int 
   fin.sap_start = s0; fin.sap_end = s1;
   if (nf.on) { fin.nap_rs = o.nap_rs; fin.nap_tiles = nf.Rp / 16; fin.nap_scale = 1.f / (float)nf.R; }
   fin.out = out; fin.flags = flags; fin.thresholds = thr;
-  return rows == 16 ? mmad_online_finish(fin, st) : mmad_online_finish64(fin, st);
+  return mmad_online_finish(fin, rows, st);
 }
 
 int64_t mmad_ae_online_groups_bytes(const mmad_ae* h, int rows) {
@@ -193,7 +188,7 @@ static int online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_sta
   const char* sfx = rows == 16 ? "" : "64";
   MMAD_CHECK_ARG(B >= 1 && B <= rows, "ae_online_score%s: B=%d outside 1..%d (the batch path, "
                  "mmad_ae_score_stream, serves larger calls)", sfx, B, rows);
-  const int64_t need = rows == 16 ? mmad_ae_online_state_bytes(h) : mmad_ae_online_state_bytes64(h);
+  const int64_t need = online_state_bytes(h, rows);
   MMAD_CHECK_ARG(state && state_bytes >= need, "ae_online_score: online state null or too small "
                  "(%lld < %lld bytes, mmad_ae_online_state_bytes%s)", (long long)(state ? state_bytes : 0),
                  (long long)need, sfx);

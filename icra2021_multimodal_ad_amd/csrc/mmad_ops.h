@@ -24,28 +24,28 @@ int mmad_vib_reparam_fwd_dyn(int dtype, int B, int btl, int k, const void* enc_o
                              int deterministic, void* z, int ld_z, float* kl_partial,
                              const MmadDyn* dyn, void* stream);
 
-// ---- 16-row weight-streaming operator and the online pass (mmad_skinny.hip)
-// y[16][Np] = epi(x[16][Kp] . w[Np][Kp]^T), M <= 16 valid rows (mmad_fc_rows16)
+// ---- weight-streaming operator and the online pass (mmad_skinny.hip)
+// y[rows][Np] = epi(x[rows][Kp] . w[Np][Kp]^T), M <= rows valid rows
+// (mmad_fc_rows16: rows = 16, mmad_fc_rows64: rows = 64): ceil(M / 16) row
+// tiles computed, all `rows` rows written, nothing at or past row `rows`
 struct MmadSkinny {
+  int rows;              // 16 or 64: the packed row capacity of x, y, diff and rowsq
   int M, N, Np, Kp;
-  const void* x;         // [16][Kp] (dtype), rows >= M zero
+  const void* x;         // [rows][Kp] (dtype), rows >= M zero
   const void* w;         // [Np][Kp] (dtype)
   const float* bias;     // [Np], nullable
   int act;
   float slope;
   const float *scale, *shift;   // eval-BN affine [Np], nullable (both or neither)
-  void* y;               // [16][Np] (dtype), nullable; rows >= M and columns >= N written 0
+  void* y;               // [rows][Np] (dtype), nullable; rows >= M and columns >= N written 0
   const void* ref;       // score reference (fp32 if ref_f32, else dtype), nullable = 0
   int ref_f32, ldref;
-  float* diff;           // fp32 [16][lddiff], nullable: columns < N, rows >= M written 0
+  float* diff;           // fp32 [rows][lddiff], nullable: columns < N, rows >= M written 0
   int lddiff;
   const float* colw;     // per-column weight of d^2, nullable = 1
-  float* rowsq;          // [Np/16][16], non-null selects the score epilogue
+  float* rowsq;          // [Np/16][rows], non-null selects the score epilogue
 };
 int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream);
-// the same for M <= 64 valid rows (mmad_fc_rows64): every [16] above is [64],
-// rowsq [Np/16][64]; ceil(M / 16) row tiles computed, all 64 rows written
-int mmad_skinny_rows_launch(int dtype, const MmadSkinny& a, void* stream);
 
 #define MMAD_ONLINE_MAX_LAYERS 32
 #define MMAD_ONLINE_MAX_DIFF 16
@@ -58,21 +58,20 @@ struct MmadOnlineFold {
 };
 int mmad_online_fold(const MmadOnlineFold& f, const float* params, const float* running, float eps,
                      float* scale, float* shift, void* stream);
+// every [rows] below: the `rows` (16 or 64) that mmad_online_finish is given
 struct MmadOnlineFinish {
   int B, n_diff;                          // valid rows, diff layers (n_enc + 1)
-  const float* rs[MMAD_ONLINE_MAX_DIFF];  // row partials [tiles][16] per diff layer
+  const float* rs[MMAD_ONLINE_MAX_DIFF];  // row partials [tiles][rows] per diff layer
   int tiles[MMAD_ONLINE_MAX_DIFF], widths[MMAD_ONLINE_MAX_DIFF];
   int sap_start, sap_end;                 // clamped: 0 <= start < end <= n_diff
   const float* nap_rs;                    // NAP row partials, null = no NAP score
   int nap_tiles;
   float nap_scale;                        // 1 / R
-  float* out;                             // [n_diff + 3][16]
-  uint8_t* flags;                         // [3][16], nullable
+  float* out;                             // [n_diff + 3][rows]
+  uint8_t* flags;                         // [3][rows], nullable
   const float* thresholds;                // [3], nullable
 };
-int mmad_online_finish(const MmadOnlineFinish& f, void* stream);
-// the 64-row form: rs [tiles][64], out [n_diff + 3][64], flags [3][64]
-int mmad_online_finish64(const MmadOnlineFinish& f, void* stream);
+int mmad_online_finish(const MmadOnlineFinish& f, int rows, void* stream);
 
 // ---- column-group mean squares (mmad_group_sq, mmad_group.hip): the bounds
 // travel in the argument struct.  n_flag: rows >= n_flag get flag 0 whatever

@@ -1,17 +1,34 @@
-// 16-row weight-streaming layer operator (mmad_fc_rows16), its form for up to
-// 64 rows (mmad_fc_rows64, skinny_rows_k below) and the small kernels of the
-// online scoring pass (mmad_ae_online_score / _score64, mmad_ae_online.hip).
+// Weight-streaming layer operator for at most 16 valid rows (mmad_fc_rows16)
+// or at most 64 (mmad_fc_rows64) -- one kernel, skinny_k<T, RT>, behind both --
+// and the small kernels of the online scoring pass (mmad_ae_online_score /
+// _score64, mmad_ae_online.hip).
 //
-// y[16][N] = epi(x[16][K] . W[N][K]^T) for at most 16 valid rows: the work is
-// one pass over W, so the kernel is built as a weight stream, not as a GEMM
-// tile.  One block per 16 output columns; its waves split K in interleaved
-// chunks (wave w takes chunks w, w + NW, ...: the block's loads stay
-// contiguous along each weight row); every lane loads its MFMA B fragment
-// straight from global memory with 16-byte loads, a chunk (4 loads of W, 4 of
-// x) ahead of the MFMAs that consume it, and W never passes through LDS.  The
-// waves' 16x16 fp32 accumulators meet in LDS and wave 0 adds them in wave
-// order: no atomics, no split-K slab, no barrier between blocks, so a launch's
-// bits depend on nothing but its operands.
+// y[rows][N] = epi(x[rows][K] . W[N][K]^T); rows = 16 or 64 is the packed row
+// capacity of every buffer, M <= rows of them are valid.  The work is one pass
+// over W, so the kernel is built as a weight stream, not as a GEMM tile.  One
+// block per 16 output columns; its waves split K in interleaved chunks (wave w
+// takes chunks w, w + NW, ...: the block's loads stay contiguous along each
+// weight row); every lane loads its MFMA B fragment straight from global
+// memory with 16-byte loads, a chunk (4 loads of W, 4 of each row tile of x)
+// ahead of the MFMAs that consume it, and W never passes through LDS.
+//
+// RT = ceil(M / 16) row tiles (the instantiation, 1..4) ride one weight
+// stream: a lane loads a chunk's W fragments once and issues one MFMA group
+// per row tile, each with its own A fragments (rows 16 t + (lane & 15) of x)
+// and its own accumulator.  A row's accumulator sees the same products in the
+// same order whatever RT and rows are, so a row's bits are equal through both
+// entry points, by construction.  Row tiles >= RT are neither loaded nor
+// computed; their rows below `rows` are written as zero and nothing at or past
+// row `rows` is touched.  The waves' 16x16 fp32 accumulators meet in LDS; wave
+// t adds tile t's in wave order and runs its epilogue (waves beyond NW take
+// t + NW, ...): no atomics, no split-K slab, no barrier between blocks, so a
+// launch's bits depend on nothing but its operands.
+// ROWS (= MmadSkinny::rows) enters only the addressing -- the epilogue's tile
+// loop and the rowsq index -- and is a template argument because as a runtime
+// value it cost 2..4 VGPRs (DESIGN.md "Online scoring"); a 16-row call only
+// ever launches RT = 1, so ten instantiations: two dtypes x (1 + 4).
+// Packed layouts: x [rows][Kp], y [rows][Np], diff [rows][lddiff],
+// rowsq [Np/16][rows].
 //
 // Fragment maps (gfx950):
 //   v_mfma_f32_16x16x32_bf16: lane l holds k = 8 (l >> 4) .. + 7 of row / column
@@ -50,125 +67,15 @@ template <typename V> __device__ __forceinline__ V load_w(const V* p) {
 #endif
 }
 
-__device__ __forceinline__ void mma(floatx4& acc, const bf16x8 (&a)[U], const bf16x8 (&b)[U]) {
-#pragma unroll
-  for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b[u], acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mma(floatx4& acc, const floatx4 (&a)[U], const floatx4 (&b)[U]) {
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][j], acc, 0, 0, 0);
-}
-
-template <typename T>
-__global__ __launch_bounds__(NW * 64) void skinny_k(const MmadSkinny a) {
-  typedef typename Frag<T>::V V;
-  constexpr int KL = Frag<T>::KL;   // k per lane and load
-  constexpr int CK = 4 * KL * U;    // k per chunk: 128 (bf16) / 64 (fp32) = 256 bytes of a row
-  __shared__ floatx4 red[NW][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int c16 = lane & 15, g = lane >> 4;
-  const int n0 = blockIdx.x * 16;
-  const T* wp = (const T*)a.w + (size_t)(n0 + c16) * a.Kp + g * KL;
-  const T* xp = (const T*)a.x + (size_t)c16 * a.Kp + g * KL;
-  const int nch = a.Kp / CK;
-  floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-  V bw[U], ax[U];
-  int c = wv;
-  if (c < nch) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      bw[u] = load_w((const V*)(wp + (size_t)c * CK + u * 4 * KL));
-      ax[u] = *(const V*)(xp + (size_t)c * CK + u * 4 * KL);
-    }
-  }
-  while (c < nch) {
-    V bn[U], an[U];
-    const int cn = c + NW;
-    const bool more = cn < nch;   // wave-uniform
-    if (more) {   // the next chunk's loads fly over this chunk's MFMAs
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        bn[u] = load_w((const V*)(wp + (size_t)cn * CK + u * 4 * KL));
-        an[u] = *(const V*)(xp + (size_t)cn * CK + u * 4 * KL);
-      }
-    }
-    mma(acc, ax, bw);
-    if (!more) break;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      bw[u] = bn[u];
-      ax[u] = an[u];
-    }
-    c = cn;
-  }
-  red[wv][lane] = acc;
-  __syncthreads();
-  if (wv != 0) return;
-  floatx4 s = red[0][lane];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) s += red[w][lane];
-
-  // ---- epilogue: column n, rows 4 g + r
-  const int n = n0 + c16;
-  const bool nv = n < a.N;
-  const float b = a.bias ? a.bias[n] : 0.f;
-  const float sc = a.scale ? a.scale[n] : 1.f;
-  const float sh = a.shift ? a.shift[n] : 0.f;
-  const float cw = a.colw ? a.colw[n] : 1.f;
-  float sq[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int m = 4 * g + r;
-    const bool valid = nv && m < a.M;
-    float v = apply_act(s[r] + b, a.act, a.slope);
-    if (a.scale) v = v * sc + sh;
-    v = valid ? v : 0.f;
-    if (a.y) ((T*)a.y)[(size_t)m * a.Np + n] = from_f32<T>(v);
-    sq[r] = 0.f;
-    if (a.rowsq) {
-      float rf = 0.f;
-      if (a.ref && valid)
-        rf = a.ref_f32 ? ((const float*)a.ref)[(size_t)m * a.ldref + n]
-                       : to_f32<T>(((const T*)a.ref)[(size_t)m * a.ldref + n]);
-      const float d = v - rf;   // invalid: 0 - 0
-      if (a.diff && nv) a.diff[(size_t)m * a.lddiff + n] = d;
-      sq[r] = d * d * cw;
-    }
-  }
-  if (a.rowsq) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) sq[r] += __shfl_xor(sq[r], o);
-      if (c16 == 0) a.rowsq[(size_t)blockIdx.x * 16 + 4 * g + r] = sq[r];
-    }
-  }
-}
-
-// ---- up to 64 rows: RT = ceil(M / 16) row tiles against one weight stream
-// (mmad_fc_rows64).  skinny_k's grid, K-chunk assignment, fragment maps and W
-// loads; a lane loads a chunk's W fragments once and issues one MFMA group per
-// row tile, each with its own A fragments (rows 16 t + (lane & 15) of x) and
-// its own accumulator, so a row's accumulator sees skinny_k's products in
-// skinny_k's order and its bits are those of the same row through skinny_k.
-// W and the RT tiles of x are both loaded a chunk ahead.  Row tiles >= RT are
-// neither loaded nor computed (RT is the instantiation); their rows are
-// written as zero.  The waves' accumulators meet in LDS; wave t adds tile t's
-// in wave order and runs its epilogue (waves beyond NW take t + NW, ...).
-// Packed layouts: x [64][Kp], y [64][Np], diff [64][lddiff], rowsq [Np/16][64].
-constexpr int RTMAX = 4;
-
 template <int RT>
-__device__ __forceinline__ void mma_rows(floatx4 (&acc)[RT], const bf16x8 (&a)[RT][U], const bf16x8 (&b)[U]) {
+__device__ __forceinline__ void mma(floatx4 (&acc)[RT], const bf16x8 (&a)[RT][U], const bf16x8 (&b)[U]) {
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
     for (int t = 0; t < RT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][u], b[u], acc[t], 0, 0, 0);
 }
 template <int RT>
-__device__ __forceinline__ void mma_rows(floatx4 (&acc)[RT], const floatx4 (&a)[RT][U], const floatx4 (&b)[U]) {
+__device__ __forceinline__ void mma(floatx4 (&acc)[RT], const floatx4 (&a)[RT][U], const floatx4 (&b)[U]) {
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -178,11 +85,11 @@ __device__ __forceinline__ void mma_rows(floatx4 (&acc)[RT], const floatx4 (&a)[
         acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][u][j], b[u][j], acc[t], 0, 0, 0);
 }
 
-template <typename T, int RT>
-__global__ __launch_bounds__(NW * 64) void skinny_rows_k(const MmadSkinny a) {
+template <typename T, int RT, int ROWS>
+__global__ __launch_bounds__(NW * 64) void skinny_k(const MmadSkinny a) {
   typedef typename Frag<T>::V V;
-  constexpr int KL = Frag<T>::KL;
-  constexpr int CK = 4 * KL * U;
+  constexpr int KL = Frag<T>::KL;   // k per lane and load
+  constexpr int CK = 4 * KL * U;    // k per chunk: 128 (bf16) / 64 (fp32) = 256 bytes of a row
   __shared__ floatx4 red[NW][RT][64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int c16 = lane & 15, g = lane >> 4;
@@ -208,7 +115,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_rows_k(const MmadSkinny a) {
     V bn[U], an[RT][U];
     const int cn = c + NW;
     const bool more = cn < nch;   // wave-uniform
-    if (more) {
+    if (more) {   // the next chunk's loads fly over this chunk's MFMAs
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         bn[u] = load_w((const V*)(wp + (size_t)cn * CK + u * 4 * KL));
@@ -216,7 +123,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_rows_k(const MmadSkinny a) {
         for (int t = 0; t < RT; ++t) an[t][u] = *(const V*)(xp + t * xt + (size_t)cn * CK + u * 4 * KL);
       }
     }
-    mma_rows<RT>(acc, ax, bw);
+    mma<RT>(acc, ax, bw);
     if (!more) break;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -237,7 +144,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_rows_k(const MmadSkinny a) {
   const float sc = a.scale ? a.scale[n] : 1.f;
   const float sh = a.shift ? a.shift[n] : 0.f;
   const float cw = a.colw ? a.colw[n] : 1.f;
-  for (int t = wv; t < RTMAX; t += NW) {
+  for (int t = wv; 16 * t < ROWS; t += NW) {   // wave-uniform
     floatx4 s = {0.f, 0.f, 0.f, 0.f};   // tiles >= RT: every row is >= M
     if (t < RT) {
       s = red[0][t][lane];
@@ -269,7 +176,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_rows_k(const MmadSkinny a) {
       for (int r = 0; r < 4; ++r) {
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) sq[r] += __shfl_xor(sq[r], o);
-        if (c16 == 0) a.rowsq[(size_t)blockIdx.x * 64 + 16 * t + 4 * g + r] = sq[r];
+        if (c16 == 0) a.rowsq[(size_t)blockIdx.x * ROWS + 16 * t + 4 * g + r] = sq[r];
       }
     }
   }
@@ -294,11 +201,14 @@ __global__ __launch_bounds__(256) void online_fold_k(const MmadOnlineFold f, con
   shift[j] = t;
 }
 
-// one block: the row partials summed in tile order, BASE / SAP / NAP and flags
-__global__ __launch_bounds__(320) void online_finish_k(const MmadOnlineFinish f) {
-  __shared__ float lsq[MMAD_ONLINE_MAX_DIFF + 1][16];
-  const int j = threadIdx.x >> 4, b = threadIdx.x & 15;
-  if (j <= f.n_diff && (j < f.n_diff || f.nap_rs)) {
+// one block of 512: the row partials summed in tile order (left to right, 8
+// loads at a time, per (layer, row)), then BASE / SAP / NAP and flags.
+// rs [tiles][ROWS], out [n_diff + 3][ROWS], flags [3][ROWS]
+template <int ROWS>
+__global__ __launch_bounds__(512) void online_finish_k(const MmadOnlineFinish f) {
+  __shared__ float lsq[MMAD_ONLINE_MAX_DIFF + 1][ROWS];
+  const int b = threadIdx.x % ROWS;
+  for (int j = threadIdx.x / ROWS; j < f.n_diff + (f.nap_rs ? 1 : 0); j += 512 / ROWS) {
     const float* p = j < f.n_diff ? f.rs[j] : f.nap_rs;
     const int nt = j < f.n_diff ? f.tiles[j] : f.nap_tiles;
     float s = 0.f;
@@ -306,17 +216,17 @@ __global__ __launch_bounds__(320) void online_finish_k(const MmadOnlineFinish f)
     for (; t + 8 <= nt; t += 8) {
       float v[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(t + u) * 16 + b];
+      for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(t + u) * ROWS + b];
 #pragma unroll
       for (int u = 0; u < 8; ++u) s += v[u];
     }
-    for (; t < nt; ++t) s += p[(size_t)t * 16 + b];
+    for (; t < nt; ++t) s += p[(size_t)t * ROWS + b];
     lsq[j][b] = s;
   }
   __syncthreads();
-  if (threadIdx.x >= 16 || b >= f.B) return;
+  if (threadIdx.x >= ROWS || b >= f.B) return;
   float* out = f.out;
-  for (int l = 0; l < f.n_diff; ++l) out[l * 16 + b] = lsq[l][b];
+  for (int l = 0; l < f.n_diff; ++l) out[l * ROWS + b] = lsq[l][b];
   const float base = lsq[0][b] / (float)f.widths[0];
   float ss = 0.f;
   int wsum = 0;
@@ -325,101 +235,78 @@ __global__ __launch_bounds__(320) void online_finish_k(const MmadOnlineFinish f)
     wsum += f.widths[l];
   }
   const float sap = ss / (float)wsum;
-  out[f.n_diff * 16 + b] = base;
-  out[(f.n_diff + 1) * 16 + b] = sap;
+  out[f.n_diff * ROWS + b] = base;
+  out[(f.n_diff + 1) * ROWS + b] = sap;
   float nap = 0.f;
   if (f.nap_rs) {
     nap = lsq[f.n_diff][b] * f.nap_scale;
-    out[(f.n_diff + 2) * 16 + b] = nap;
+    out[(f.n_diff + 2) * ROWS + b] = nap;
   }
   if (f.flags) {
     // strict >: get_f1_score's prediction rule; a NaN threshold compares false
     const float* th = f.thresholds;
     f.flags[b] = th ? (uint8_t)(base > th[0]) : 0;
-    f.flags[16 + b] = th ? (uint8_t)(sap > th[1]) : 0;
-    f.flags[32 + b] = (th && f.nap_rs) ? (uint8_t)(nap > th[2]) : 0;
-  }
-}
-
-// online_finish_k for the 64-row layouts: rs [tiles][64], out [n_diff + 3][64],
-// flags [3][64]; the same left-to-right tile sum per (layer, row)
-__global__ __launch_bounds__(512) void online_finish64_k(const MmadOnlineFinish f) {
-  __shared__ float lsq[MMAD_ONLINE_MAX_DIFF + 1][64];
-  const int b = threadIdx.x & 63;
-  for (int j = threadIdx.x >> 6; j < f.n_diff + (f.nap_rs ? 1 : 0); j += 8) {
-    const float* p = j < f.n_diff ? f.rs[j] : f.nap_rs;
-    const int nt = j < f.n_diff ? f.tiles[j] : f.nap_tiles;
-    float s = 0.f;
-    int t = 0;
-    for (; t + 8 <= nt; t += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(t + u) * 64 + b];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; t < nt; ++t) s += p[(size_t)t * 64 + b];
-    lsq[j][b] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x >= 64 || b >= f.B) return;
-  float* out = f.out;
-  for (int l = 0; l < f.n_diff; ++l) out[l * 64 + b] = lsq[l][b];
-  const float base = lsq[0][b] / (float)f.widths[0];
-  float ss = 0.f;
-  int wsum = 0;
-  for (int l = f.sap_start; l < f.sap_end; ++l) {
-    ss += lsq[l][b];
-    wsum += f.widths[l];
-  }
-  const float sap = ss / (float)wsum;
-  out[f.n_diff * 64 + b] = base;
-  out[(f.n_diff + 1) * 64 + b] = sap;
-  float nap = 0.f;
-  if (f.nap_rs) {
-    nap = lsq[f.n_diff][b] * f.nap_scale;
-    out[(f.n_diff + 2) * 64 + b] = nap;
-  }
-  if (f.flags) {
-    const float* th = f.thresholds;
-    f.flags[b] = th ? (uint8_t)(base > th[0]) : 0;
-    f.flags[64 + b] = th ? (uint8_t)(sap > th[1]) : 0;
-    f.flags[128 + b] = (th && f.nap_rs) ? (uint8_t)(nap > th[2]) : 0;
+    f.flags[ROWS + b] = th ? (uint8_t)(sap > th[1]) : 0;
+    f.flags[2 * ROWS + b] = (th && f.nap_rs) ? (uint8_t)(nap > th[2]) : 0;
   }
 }
 
 template <typename T>
-void launch_rows(const MmadSkinny& a, hipStream_t s) {
+void launch(const MmadSkinny& a, hipStream_t s) {
   const dim3 grid(a.Np / 16), block(NW * 64);
-  switch ((a.M + 15) / 16) {
-    case 1: skinny_rows_k<T, 1><<<grid, block, 0, s>>>(a); break;
-    case 2: skinny_rows_k<T, 2><<<grid, block, 0, s>>>(a); break;
-    case 3: skinny_rows_k<T, 3><<<grid, block, 0, s>>>(a); break;
-    default: skinny_rows_k<T, 4><<<grid, block, 0, s>>>(a); break;
+  if (a.rows == 16) {   // M <= rows: a 16-row call only ever takes RT = 1
+    skinny_k<T, 1, 16><<<grid, block, 0, s>>>(a);
+    return;
   }
+  switch ((a.M + 15) / 16) {
+    case 1: skinny_k<T, 1, 64><<<grid, block, 0, s>>>(a); break;
+    case 2: skinny_k<T, 2, 64><<<grid, block, 0, s>>>(a); break;
+    case 3: skinny_k<T, 3, 64><<<grid, block, 0, s>>>(a); break;
+    default: skinny_k<T, 4, 64><<<grid, block, 0, s>>>(a); break;
+  }
+}
+
+// mmad_fc_rows16 / mmad_fc_rows64: the C-ABI arguments into MmadSkinny
+int fc_rows(int rows, int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
+            const float* bias, int act, float slope, const float* bn_scale, const float* bn_shift, void* y,
+            const void* ref, int ref_dtype, int ldref, float* diff, int lddiff, const float* colw,
+            float* rowsq, void* stream) {
+  MMAD_CHECK_ARG(K >= 1 && K <= Kp, "fc_rows%d: K=%d outside 1..Kp=%d", rows, K, Kp);
+  MMAD_CHECK_ARG(!bn_scale == !bn_shift, "fc_rows%d: bn_scale and bn_shift go together", rows);
+  MMAD_CHECK_ARG(!ref || ((ref_dtype == MMAD_F32 || ref_dtype == dtype) && ldref >= N),
+                 "fc_rows%d: ref is fp32 or the operand dtype, ldref >= N", rows);
+  MMAD_CHECK_ARG(!diff || lddiff >= N, "fc_rows%d: lddiff < N", rows);
+  MmadSkinny a{};
+  a.rows = rows; a.M = M; a.N = N; a.Np = Np; a.Kp = Kp;
+  a.x = x; a.w = w; a.bias = bias; a.act = act; a.slope = slope;
+  a.scale = bn_scale; a.shift = bn_shift; a.y = y;
+  a.ref = ref; a.ref_f32 = ref_dtype == MMAD_F32; a.ldref = ldref;
+  a.diff = diff; a.lddiff = lddiff; a.colw = colw; a.rowsq = rowsq;
+  return mmad_skinny_launch(dtype, a, stream);
 }
 
 }  // namespace
 
 int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream) {
-  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16, "fc_rows16: dtype %d (MMAD_F32 or MMAD_BF16)", dtype);
-  MMAD_CHECK_ARG(a.M >= 1 && a.M <= 16, "fc_rows16: M=%d outside 1..16", a.M);
+  const int R = a.rows;
+  MMAD_CHECK_ARG(R == 16 || R == 64, "fc_rows: rows=%d (16 or 64)", R);
+  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16, "fc_rows%d: dtype %d (MMAD_F32 or MMAD_BF16)", R, dtype);
+  MMAD_CHECK_ARG(a.M >= 1 && a.M <= R, "fc_rows%d: M=%d outside 1..%d", R, a.M, R);
   MMAD_CHECK_ARG(a.N >= 1 && a.N <= a.Np && a.Np % 16 == 0 && a.Kp >= MMAD_PAD && a.Kp % MMAD_PAD == 0,
-                 "fc_rows16: bad sizes N=%d Np=%d Kp=%d (Np a multiple of 16, Kp of %d)", a.N, a.Np, a.Kp,
+                 "fc_rows%d: bad sizes N=%d Np=%d Kp=%d (Np a multiple of 16, Kp of %d)", R, a.N, a.Np, a.Kp,
                  MMAD_PAD);
   MMAD_CHECK_ARG(a.x && a.w && ((uintptr_t)a.x | (uintptr_t)a.w) % 16 == 0,
-                 "fc_rows16: x and w must be non-null and 16-byte aligned");
-  MMAD_CHECK_ARG(a.y || a.rowsq, "fc_rows16: neither y nor rowsq to write");
-  MMAD_CHECK_ARG(a.rowsq || (!a.ref && !a.diff && !a.colw), "fc_rows16: ref / diff / colw need rowsq");
+                 "fc_rows%d: x and w must be non-null and 16-byte aligned", R);
+  MMAD_CHECK_ARG(a.y || a.rowsq, "fc_rows%d: neither y nor rowsq to write", R);
+  MMAD_CHECK_ARG(a.rowsq || (!a.ref && !a.diff && !a.colw), "fc_rows%d: ref / diff / colw need rowsq", R);
   if (a.act < MMAD_ACT_NONE || a.act > MMAD_ACT_TANH) {
-    mmad_set_error("fc_rows16: activation %d has no per-element epilogue", a.act);
+    mmad_set_error("fc_rows%d: activation %d has no per-element epilogue", R, a.act);
     return MMAD_EUNSUPPORTED;
   }
-  hipStream_t s = (hipStream_t)stream;
   if (dtype == MMAD_BF16)
-    skinny_k<bf16><<<a.Np / 16, NW * 64, 0, s>>>(a);
+    launch<bf16>(a, (hipStream_t)stream);
   else
-    skinny_k<float><<<a.Np / 16, NW * 64, 0, s>>>(a);
+    launch<float>(a, (hipStream_t)stream);
   MMAD_LAUNCH_CHECK();
   return MMAD_OK;
 }
@@ -428,58 +315,16 @@ int mmad_fc_rows16(int dtype, int M, int N, int K, int Np, int Kp, const void* x
                    const float* bias, int act, float slope, const float* bn_scale, const float* bn_shift,
                    void* y, const void* ref, int ref_dtype, int ldref, float* diff, int lddiff,
                    const float* colw, float* rowsq, void* stream) {
-  MMAD_CHECK_ARG(K >= 1 && K <= Kp, "fc_rows16: K=%d outside 1..Kp=%d", K, Kp);
-  MMAD_CHECK_ARG(!bn_scale == !bn_shift, "fc_rows16: bn_scale and bn_shift go together");
-  MMAD_CHECK_ARG(!ref || ((ref_dtype == MMAD_F32 || ref_dtype == dtype) && ldref >= N),
-                 "fc_rows16: ref is fp32 or the operand dtype, ldref >= N");
-  MMAD_CHECK_ARG(!diff || lddiff >= N, "fc_rows16: lddiff < N");
-  MmadSkinny a{};
-  a.M = M; a.N = N; a.Np = Np; a.Kp = Kp;
-  a.x = x; a.w = w; a.bias = bias; a.act = act; a.slope = slope;
-  a.scale = bn_scale; a.shift = bn_shift; a.y = y;
-  a.ref = ref; a.ref_f32 = ref_dtype == MMAD_F32; a.ldref = ldref;
-  a.diff = diff; a.lddiff = lddiff; a.colw = colw; a.rowsq = rowsq;
-  return mmad_skinny_launch(dtype, a, stream);
-}
-
-int mmad_skinny_rows_launch(int dtype, const MmadSkinny& a, void* stream) {
-  MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16, "fc_rows64: dtype %d (MMAD_F32 or MMAD_BF16)", dtype);
-  MMAD_CHECK_ARG(a.M >= 1 && a.M <= 16 * RTMAX, "fc_rows64: M=%d outside 1..64", a.M);
-  MMAD_CHECK_ARG(a.N >= 1 && a.N <= a.Np && a.Np % 16 == 0 && a.Kp >= MMAD_PAD && a.Kp % MMAD_PAD == 0,
-                 "fc_rows64: bad sizes N=%d Np=%d Kp=%d (Np a multiple of 16, Kp of %d)", a.N, a.Np, a.Kp,
-                 MMAD_PAD);
-  MMAD_CHECK_ARG(a.x && a.w && ((uintptr_t)a.x | (uintptr_t)a.w) % 16 == 0,
-                 "fc_rows64: x and w must be non-null and 16-byte aligned");
-  MMAD_CHECK_ARG(a.y || a.rowsq, "fc_rows64: neither y nor rowsq to write");
-  MMAD_CHECK_ARG(a.rowsq || (!a.ref && !a.diff && !a.colw), "fc_rows64: ref / diff / colw need rowsq");
-  if (a.act < MMAD_ACT_NONE || a.act > MMAD_ACT_TANH) {
-    mmad_set_error("fc_rows64: activation %d has no per-element epilogue", a.act);
-    return MMAD_EUNSUPPORTED;
-  }
-  if (dtype == MMAD_BF16)
-    launch_rows<bf16>(a, (hipStream_t)stream);
-  else
-    launch_rows<float>(a, (hipStream_t)stream);
-  MMAD_LAUNCH_CHECK();
-  return MMAD_OK;
+  return fc_rows(16, dtype, M, N, K, Np, Kp, x, w, bias, act, slope, bn_scale, bn_shift, y, ref, ref_dtype,
+                 ldref, diff, lddiff, colw, rowsq, stream);
 }
 
 int mmad_fc_rows64(int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
                    const float* bias, int act, float slope, const float* bn_scale, const float* bn_shift,
                    void* y, const void* ref, int ref_dtype, int ldref, float* diff, int lddiff,
                    const float* colw, float* rowsq, void* stream) {
-  MMAD_CHECK_ARG(K >= 1 && K <= Kp, "fc_rows64: K=%d outside 1..Kp=%d", K, Kp);
-  MMAD_CHECK_ARG(!bn_scale == !bn_shift, "fc_rows64: bn_scale and bn_shift go together");
-  MMAD_CHECK_ARG(!ref || ((ref_dtype == MMAD_F32 || ref_dtype == dtype) && ldref >= N),
-                 "fc_rows64: ref is fp32 or the operand dtype, ldref >= N");
-  MMAD_CHECK_ARG(!diff || lddiff >= N, "fc_rows64: lddiff < N");
-  MmadSkinny a{};
-  a.M = M; a.N = N; a.Np = Np; a.Kp = Kp;
-  a.x = x; a.w = w; a.bias = bias; a.act = act; a.slope = slope;
-  a.scale = bn_scale; a.shift = bn_shift; a.y = y;
-  a.ref = ref; a.ref_f32 = ref_dtype == MMAD_F32; a.ldref = ldref;
-  a.diff = diff; a.lddiff = lddiff; a.colw = colw; a.rowsq = rowsq;
-  return mmad_skinny_rows_launch(dtype, a, stream);
+  return fc_rows(64, dtype, M, N, K, Np, Kp, x, w, bias, act, slope, bn_scale, bn_shift, y, ref, ref_dtype,
+                 ldref, diff, lddiff, colw, rowsq, stream);
 }
 
 int mmad_online_fold(const MmadOnlineFold& f, const float* params, const float* running, float eps,
@@ -490,16 +335,13 @@ int mmad_online_fold(const MmadOnlineFold& f, const float* params, const float* 
   return MMAD_OK;
 }
 
-int mmad_online_finish(const MmadOnlineFinish& f, void* stream) {
+int mmad_online_finish(const MmadOnlineFinish& f, int rows, void* stream) {
   MMAD_CHECK_ARG(f.n_diff >= 1 && f.n_diff <= MMAD_ONLINE_MAX_DIFF, "online_finish: %d diff layers", f.n_diff);
-  online_finish_k<<<1, 320, 0, (hipStream_t)stream>>>(f);
-  MMAD_LAUNCH_CHECK();
-  return MMAD_OK;
-}
-
-int mmad_online_finish64(const MmadOnlineFinish& f, void* stream) {
-  MMAD_CHECK_ARG(f.n_diff >= 1 && f.n_diff <= MMAD_ONLINE_MAX_DIFF, "online_finish: %d diff layers", f.n_diff);
-  online_finish64_k<<<1, 512, 0, (hipStream_t)stream>>>(f);
+  MMAD_CHECK_ARG(rows == 16 || rows == 64, "online_finish: rows=%d (16 or 64)", rows);
+  if (rows == 16)
+    online_finish_k<16><<<1, 512, 0, (hipStream_t)stream>>>(f);
+  else
+    online_finish_k<64><<<1, 512, 0, (hipStream_t)stream>>>(f);
   MMAD_LAUNCH_CHECK();
   return MMAD_OK;
 }

@@ -2,11 +2,9 @@
 (mmad_fc_rows16), the whole pass (mmad_ae_online_score) and the Python surface
 (online.OnlineScorer, NoveltyDetecter.online_scorer).
 
-Models follow tests/test_gpu_nap_stream.py::_model: the mm192 golden, widths
-[192, 156, 121, 86, 51, 16] -- no layer width is a multiple of 16 and the diff
-columns of the NAP operand start at odd offsets.  Figures go to
+Models, fit and buffers are those of tests/online_fixture.py (the mm192 golden,
+widths [192, 156, 121, 86, 51, 16]).  Figures go to
 $MMAD_RECORD_DIR/online.json (default test_records/)."""
-import ctypes
 import json
 import os
 import types
@@ -16,12 +14,12 @@ import pytest
 import torch
 
 from icra2021_multimodal_ad_amd import _native
-from icra2021_multimodal_ad_amd._native import call, pad, ptr, stream_ptr
 from icra2021_multimodal_ad_amd.data import synth_windows
+from tests.online_fixture import (BF16, F32, VARIANTS, X3, _fit, _graphs, _model, _Rig, _sd,
+                                  check_fc_rows_against_fp64)
 
 pytestmark = pytest.mark.gpu
 
-F32, BF16, X3 = 0, 1, 2
 _REC = {}
 
 
@@ -32,173 +30,18 @@ def _record():
         json.dump(_REC, f, indent=1, default=float)
 
 
-def _sd(g, prefix):
-    return {k[len(prefix):]: g[k] for k in g.files if k.startswith(prefix)}
-
-
-def _model(golden, dtype="f32", score_dtype=None, step=None, models="ae"):
-    from icra2021_multimodal_ad_amd.model_builder import get_model
-    g = golden("mm192")
-    cfg = types.SimpleNamespace(input_size=int(g["meta_d"]), btl_size=int(g["meta_btl"]),
-                                n_layers=int(g["meta_n_layers"]), gpu_id=0, dtype=dtype, models=models)
-    if score_dtype is not None:
-        cfg.score_dtype = score_dtype
-    m = get_model(cfg)
-    if models == "ae":
-        step = int(g["meta_steps"]) - 1 if step is None else step
-        sd = _sd(g, f"after{step}/")
-        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
-    m.eval()
-    return m
-
-
-def _fit(m, rng_=(0, 6), n_train=300, seed=11):
-    """A NapScorer fitted on the model's own train diffs of the layer range."""
-    from icra2021_multimodal_ad_amd.reconstruction_aggregation import NapScorer
-    nat = m._native
-    cuts = np.cumsum([0] + nat.diff_widths())
-    c0, c1 = int(cuts[rng_[0]]), int(cuts[rng_[1]])
-    xt = torch.from_numpy(synth_windows(n_train, nat.enc_widths[0], seed=seed)).cuda()
-    train = nat.score(xt, want_diffs=True)[1][:, c0:c1].contiguous()
-    return NapScorer.standalone(c1 - c0, device=nat.device).fit(train_diffs=train)
-
-
-class _Rig:
-    """Fixed buffers for raw mmad_ae_online_score calls on one model."""
-
-    def __init__(self, m, canary=-7.0):
-        self.nat = nat = m._native
-        self.canary = canary
-        self.x = torch.zeros((16, nat.enc_widths[0]), device="cuda")
-        self.out = torch.full((nat.n_enc + 4, 16), canary, device="cuda")
-        self.flags = torch.full((3, 16), 9, device="cuda", dtype=torch.uint8)
-        self.thr = torch.full((3,), float("nan"), device="cuda")
-        self.state = nat.online_state()
-
-    def run(self, x, graph=False, start=0, end=None, fresh=False):
-        B = x.shape[0]
-        self.x[:B].copy_(x)
-        self.out.fill_(self.canary)
-        self.flags.fill_(9)
-        if fresh:
-            self.state = self.nat.online_state()
-        self.nat.online_score(self.x, B, self.out, self.state, flags=self.flags, thresholds=self.thr,
-                              start=start, end=end, graph=graph)
-        torch.cuda.synchronize()
-        return self.out.clone(), self.flags.clone()
-
-
-def _graphs(nat):
-    return nat._lib.mmad_ae_graph_count(nat._h)
-
-
 # ------------------------------------------------- 1. the operator vs fp64 numpy
-def _vec(v, Np):
-    if v is None:
-        return None
-    p = torch.zeros(Np, device="cuda")
-    p[:v.numel()] = v
-    return p
-
-
-# (act, BN affine, score epilogue, ref, colw)
-VARIANTS = [(0, False, False, False, False), (1, True, False, False, False), (1, True, True, True, False),
-            (0, False, True, False, True), (1, False, True, True, True)]
-
-
 @pytest.mark.parametrize("variant", VARIANTS, ids=lambda v: "act%d-bn%d-score%d-ref%d-colw%d" % tuple(map(int, v)))
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("M,N,K", [(1, 1, 1), (10, 130, 70), (16, 128, 2048), (7, 100, 6442)])
 def test_fc_rows16_against_fp64(M, N, K, dtype, variant):
-    """max |err| / (sum_k |a||b| + |bias|) (carried through the BN affine, the
-    measure of tests/test_gpu_x3.py) of mmad_fc_rows16 at most twice the same
-    figure of the parent's mmad_fc_fwd / mmad_fc_fwd_score on the same
-    operands: both are fp32 accumulations that differ only in association.
-    With the score epilogue the figure is taken on the diff output.  Exact:
-    rows >= M of y are zero, rows >= M / columns >= N are absent from rowsq,
-    the canaries around diff's written region are intact; rowsq itself equals
-    the fp64 sum of colw d^2 over each tile's columns of the kernel's own diff
-    within 8 * 2^-24 relative (two products per term and a 4-level tree of
-    non-negative fp32 adds)."""
-    act, affine, score, use_ref, use_colw = variant
-    rng = np.random.default_rng(1000 * M + 10 * N + K)
-    x = rng.standard_normal((M, K)).astype(np.float32)
-    w = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
-    b = (0.1 * rng.standard_normal(N)).astype(np.float32)
-    sc = rng.uniform(0.5, 1.5, N).astype(np.float32) if affine else None
-    sh = (0.1 * rng.standard_normal(N)).astype(np.float32) if affine else None
-    rf = rng.standard_normal((M, N)).astype(np.float32) if use_ref else None
-    cw = rng.uniform(0.5, 2.0, N).astype(np.float32) if use_colw else None
-    tdt = torch.float32 if dtype == F32 else torch.bfloat16
-    if rf is not None:
-        rf = torch.from_numpy(rf).to(tdt).float().numpy()          # representable in the operand dtype
-    x64, w64 = x.astype(np.float64), w.astype(np.float64)
-    z = x64 @ w64.T + b
-    ref = np.where(z > 0, z, 0.2 * z) if act == 1 else z
-    den = np.abs(x64) @ np.abs(w64).T + np.abs(b)
-    if affine:
-        ref = ref * sc + sh
-        den = den * np.abs(sc) + np.abs(sh)
-    if use_ref:
-        ref = ref - rf
-    Mp, Kp, Np = pad(M), pad(K), pad(N)
-    s = stream_ptr()
-    dx, dw = torch.from_numpy(x).cuda(), torch.from_numpy(w).cuda()
-    x16 = torch.empty((16, Kp), device="cuda", dtype=tdt)
-    xin = torch.empty((Mp, Kp), device="cuda", dtype=tdt)
-    wp = torch.empty((Np, Kp), device="cuda", dtype=tdt)
-    call("mmad_pack_input", dtype, M, K, 16, Kp, ptr(dx), K, ptr(x16), s)
-    call("mmad_pack_input", dtype, M, K, Mp, Kp, ptr(dx), K, ptr(xin), s)
-    call("mmad_pack_input", dtype, N, K, Np, Kp, ptr(dw), K, ptr(wp), s)
-    bp, scp, shp, cwp = (_vec(None if v is None else torch.from_numpy(v).cuda(), Np) for v in (b, sc, sh, cw))
-    refp = None
-    if use_ref:
-        refp = torch.zeros((Mp, Np), device="cuda", dtype=tdt)
-        refp[:M, :N] = torch.from_numpy(rf).cuda().to(tdt)
-    # the parent's kernel on the same operands
-    yp = torch.empty((Mp, Np), device="cuda", dtype=tdt)
-    if use_ref:
-        rsq = torch.empty((Np // 128, Mp), device="cuda")
-        dparent = torch.zeros((M, N), device="cuda")
-        call("mmad_fc_fwd_score", dtype, M, N, K, Mp, Np, Kp, ptr(xin), ptr(wp), ptr(bp), act, 0.2, ptr(scp),
-             ptr(shp), ptr(yp), ptr(refp), ptr(rsq), ptr(dparent), N, s)
-        parent = dparent.double().cpu().numpy()
-    else:
-        call("mmad_fc_fwd", dtype, M, N, K, Mp, Np, Kp, ptr(xin), ptr(wp), ptr(bp), act, 0.2, ptr(scp),
-             ptr(shp), ptr(yp), None, s)
-        parent = yp[:M, :N].double().cpu().numpy()
-    # the 16-row operator; diff sits inside a canary frame at an odd column
-    y = torch.full((17, Np), 5.0, device="cuda", dtype=tdt)
-    ld, c0 = N + 7, 3
-    diff = torch.full((18, ld), 77.0, device="cuda")
-    rowsq = torch.full((Np // 16 + 1, 16), 55.0, device="cuda")
-    call("mmad_fc_rows16", dtype, M, N, K, Np, Kp, ptr(x16), ptr(wp), ptr(bp), act, 0.2, ptr(scp), ptr(shp),
-         ptr(y), ptr(refp), dtype, Np, ptr(diff[0, c0:]) if score else None, ld, ptr(cwp),
-         ptr(rowsq) if score else None, s)
-    torch.cuda.synchronize()
-    got = (diff[:M, c0:c0 + N] if score else y[:M, :N]).double().cpu().numpy()
-    e_new = float((np.abs(got - ref) / den).max())
-    e_old = float((np.abs(parent - ref) / den).max())
-    key = f"fc_rows16/{'bf16' if dtype == BF16 else 'f32'}/{M}x{N}x{K}/" + "".join(str(int(v)) for v in variant)
-    _REC[key] = {"rows16": e_new, "parent": e_old}
-    _record()
-    print(f"\n{key}: rows16 {e_new:.3e} parent {e_old:.3e}")
-    assert (y[M:16] == 0).all() and (y[:16, N:] == 0).all() and (y[16] == 5.0).all()
-    if score:
-        assert (diff[M:16, c0:c0 + N] == 0).all()                     # rows >= M: written as zero
-        assert (diff[:, :c0] == 77.0).all() and (diff[:, c0 + N:] == 77.0).all() and (diff[16:] == 77.0).all()
-        assert (rowsq[-1] == 55.0).all()
-        rs = rowsq[:-1].double().cpu().numpy()                        # [tiles][16]
-        assert (rs[:, M:] == 0).all()
-        d = np.zeros((16, Np))
-        d[:M, :N] = got
-        wgt = np.ones(Np) if cw is None else np.r_[cw.astype(np.float64), np.zeros(Np - N)]
-        want = ((d * d * wgt).reshape(16, Np // 16, 16).sum(-1)).T    # columns >= N: d = 0
-        assert (rs[N // 16 + 1:] == 0).all()
-        assert np.all(np.abs(rs - want) <= 8 * 2.0 ** -24 * want + 1e-300)
-    else:
-        assert (rowsq == 55.0).all() and (diff == 77.0).all()
-    assert e_new <= 2 * e_old
+    """The bars of tests/online_fixture.py::check_fc_rows_against_fp64 on
+    mmad_fc_rows16; the figures go to online.json under fc_rows16/..."""
+    def record(key, figures):
+        _REC[key] = figures
+        _record()
+
+    check_fc_rows_against_fp64(16, M, N, K, dtype, variant, record)
 
 
 # ----------------------------------------------- 2. whole pass vs the fp64 oracle

@@ -1,7 +1,7 @@
 """Per-modality scores from the online pass (mmad_ae_online_score_groups,
 OnlineScorer(groups=...)) and the batch route (group_scores) on the GPU.
 
-Models are the mm192 golden of tests/test_gpu_online.py (widths [192, 156, 121,
+Models are the mm192 golden of tests/online_fixture.py (widths [192, 156, 121,
 86, 51, 16]); its input row is cut into four groups at columns no multiple of
 4, and into two groups that leave both ends of the row out."""
 import types
@@ -13,7 +13,8 @@ import torch
 from icra2021_multimodal_ad_amd import _native
 from icra2021_multimodal_ad_amd.data import synth_windows
 from icra2021_multimodal_ad_amd.online import OnlineScorer
-from icra2021_multimodal_ad_amd.reconstruction_aggregation import NapScorer, group_scores
+from icra2021_multimodal_ad_amd.reconstruction_aggregation import group_scores
+from tests.online_fixture import _fit, _graphs, _model
 
 pytestmark = pytest.mark.gpu
 
@@ -21,33 +22,6 @@ GROUPS = {"a": (0, 101), "b": (101, 107), "c": (107, 171), "d": (171, 192)}   # 
 BOUNDS = [0, 101, 107, 171, 192]
 INNER = [(3, 64), (64, 190)]
 THR = {"base": 0.05, "sap": 0.05, "nap": 1.0, "groups": {"a": 0.05, "b": 0.01, "c": -1.0}}   # d: NaN
-
-
-def _sd(g, prefix):
-    return {k[len(prefix):]: g[k] for k in g.files if k.startswith(prefix)}
-
-
-def _model(golden, dtype="f32", models="ae"):
-    from icra2021_multimodal_ad_amd.model_builder import get_model
-    g = golden("mm192")
-    cfg = types.SimpleNamespace(input_size=int(g["meta_d"]), btl_size=int(g["meta_btl"]),
-                                n_layers=int(g["meta_n_layers"]), gpu_id=0, dtype=dtype, models=models)
-    m = get_model(cfg)
-    if models == "ae":
-        sd = _sd(g, f"after{int(g['meta_steps']) - 1}/")
-        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
-    m.eval()
-    return m
-
-
-def _fit(m, rng_, n_train=300, seed=11):
-    """A standalone NapScorer fitted on the model's own train diffs of the diff layers rng_."""
-    nat = m._native
-    cuts = np.cumsum([0] + nat.diff_widths())
-    c0, c1 = int(cuts[rng_[0]]), int(cuts[rng_[1]])
-    xt = torch.from_numpy(synth_windows(n_train, nat.enc_widths[0], seed=seed)).cuda()
-    train = nat.score(xt, want_diffs=True)[1][:, c0:c1].contiguous()
-    return NapScorer.standalone(c1 - c0, device=nat.device).fit(train_diffs=train)
 
 
 @pytest.fixture(scope="module")
@@ -79,10 +53,6 @@ def _scorer(m, fits, route, rows, groups=None, thresholds=THR):
 
 def _keep(res):
     return {k: v.clone() for k, v in res.items() if v is not None}
-
-
-def _graphs(nat):
-    return nat._lib.mmad_ae_graph_count(nat._h)
 
 
 # ------------------------------------------------------ 5. nothing existing moves

@@ -4,8 +4,9 @@ Python surface (OnlineScorer(rows=64), NoveltyDetecter.online_scorer).
 
 The design constraint is bit equality with the 16-row path: a row's
 accumulator sees the same products in the same order, so every comparison
-against mmad_fc_rows16 / mmad_ae_online_score below is torch.equal.  Models
-and the fitted NAP are those of tests/test_gpu_online.py (the mm192 golden)."""
+against mmad_fc_rows16 / mmad_ae_online_score below is torch.equal.  Models,
+the fitted NAP and the buffers are those of tests/online_fixture.py (the
+mm192 golden)."""
 import types
 
 import numpy as np
@@ -15,15 +16,10 @@ import torch
 from icra2021_multimodal_ad_amd import _native
 from icra2021_multimodal_ad_amd._native import call, pad, ptr, stream_ptr
 from icra2021_multimodal_ad_amd.data import synth_windows
-from tests.test_gpu_online import VARIANTS, _fit, _model, _vec
+from tests.online_fixture import (BF16, F32, VARIANTS, X3, _fit, _graphs, _model, _Rig, _vec,
+                                  check_fc_rows_against_fp64)
 
 pytestmark = pytest.mark.gpu
-
-F32, BF16, X3 = 0, 1, 2
-
-
-def _graphs(nat):
-    return nat._lib.mmad_ae_graph_count(nat._h)
 
 
 # ------------------------------------ 1. the operator's rows vs the 16-row kernel
@@ -124,118 +120,12 @@ def test_fc_rows64_rows_equal_fc_rows16_bitwise(N, K, M, dtype, variant):
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("M,N,K", [(40, 130, 70), (64, 100, 896)])
 def test_fc_rows64_against_fp64(M, N, K, dtype, variant):
-    """The bars of tests/test_gpu_online.py::test_fc_rows16_against_fp64 on the
-    64-row layouts: max |err| / (sum_k |a||b| + |bias|), carried through the BN
-    affine, at most twice the same figure of mmad_fc_fwd / mmad_fc_fwd_score on
-    the same operands (with the score epilogue: on the diff output); rows >= M
-    of y zero, rows >= M / columns >= N absent from rowsq, the canaries around
-    diff's written region intact; rowsq equal to the fp64 sum of colw d^2 over
-    each tile's columns of the kernel's own diff within 8 * 2^-24 relative."""
-    act, affine, score, use_ref, use_colw = variant
-    rng = np.random.default_rng(1000 * M + 10 * N + K)
-    x = rng.standard_normal((M, K)).astype(np.float32)
-    w = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
-    b = (0.1 * rng.standard_normal(N)).astype(np.float32)
-    sc = rng.uniform(0.5, 1.5, N).astype(np.float32) if affine else None
-    sh = (0.1 * rng.standard_normal(N)).astype(np.float32) if affine else None
-    rf = rng.standard_normal((M, N)).astype(np.float32) if use_ref else None
-    cw = rng.uniform(0.5, 2.0, N).astype(np.float32) if use_colw else None
-    tdt = torch.float32 if dtype == F32 else torch.bfloat16
-    if rf is not None:
-        rf = torch.from_numpy(rf).to(tdt).float().numpy()          # representable in the operand dtype
-    x64, w64 = x.astype(np.float64), w.astype(np.float64)
-    z = x64 @ w64.T + b
-    ref = np.where(z > 0, z, 0.2 * z) if act == 1 else z
-    den = np.abs(x64) @ np.abs(w64).T + np.abs(b)
-    if affine:
-        ref = ref * sc + sh
-        den = den * np.abs(sc) + np.abs(sh)
-    if use_ref:
-        ref = ref - rf
-    Mp, Kp, Np = pad(M), pad(K), pad(N)
-    s = stream_ptr()
-    dx, dw = torch.from_numpy(x).cuda(), torch.from_numpy(w).cuda()
-    xr = torch.empty((64, Kp), device="cuda", dtype=tdt)
-    xin = torch.empty((Mp, Kp), device="cuda", dtype=tdt)
-    wp = torch.empty((Np, Kp), device="cuda", dtype=tdt)
-    call("mmad_pack_input", dtype, M, K, 64, Kp, ptr(dx), K, ptr(xr), s)
-    call("mmad_pack_input", dtype, M, K, Mp, Kp, ptr(dx), K, ptr(xin), s)
-    call("mmad_pack_input", dtype, N, K, Np, Kp, ptr(dw), K, ptr(wp), s)
-    bp, scp, shp, cwp = (_vec(None if v is None else torch.from_numpy(v).cuda(), Np) for v in (b, sc, sh, cw))
-    refp = None
-    if use_ref:
-        refp = torch.zeros((Mp, Np), device="cuda", dtype=tdt)
-        refp[:M, :N] = torch.from_numpy(rf).cuda().to(tdt)
-    # the batch path's kernel on the same operands
-    yp = torch.empty((Mp, Np), device="cuda", dtype=tdt)
-    if use_ref:
-        rsq = torch.empty((Np // 128, Mp), device="cuda")
-        dparent = torch.zeros((M, N), device="cuda")
-        call("mmad_fc_fwd_score", dtype, M, N, K, Mp, Np, Kp, ptr(xin), ptr(wp), ptr(bp), act, 0.2, ptr(scp),
-             ptr(shp), ptr(yp), ptr(refp), ptr(rsq), ptr(dparent), N, s)
-        parent = dparent.double().cpu().numpy()
-    else:
-        call("mmad_fc_fwd", dtype, M, N, K, Mp, Np, Kp, ptr(xin), ptr(wp), ptr(bp), act, 0.2, ptr(scp),
-             ptr(shp), ptr(yp), None, s)
-        parent = yp[:M, :N].double().cpu().numpy()
-    # the 64-row operator; diff sits inside a canary frame at an odd column
-    y = torch.full((65, Np), 5.0, device="cuda", dtype=tdt)
-    ld, c0 = N + 7, 3
-    diff = torch.full((66, ld), 77.0, device="cuda")
-    rowsq = torch.full((Np // 16 + 1, 64), 55.0, device="cuda")
-    call("mmad_fc_rows64", dtype, M, N, K, Np, Kp, ptr(xr), ptr(wp), ptr(bp), act, 0.2, ptr(scp), ptr(shp),
-         ptr(y), ptr(refp), dtype, Np, ptr(diff[0, c0:]) if score else None, ld, ptr(cwp),
-         ptr(rowsq) if score else None, s)
-    torch.cuda.synchronize()
-    got = (diff[:M, c0:c0 + N] if score else y[:M, :N]).double().cpu().numpy()
-    e_new = float((np.abs(got - ref) / den).max())
-    e_old = float((np.abs(parent - ref) / den).max())
-    print(f"\nfc_rows64/{'bf16' if dtype == BF16 else 'f32'}/{M}x{N}x{K}/{variant}: rows64 {e_new:.3e} "
-          f"batch kernel {e_old:.3e}")
-    assert (y[M:64] == 0).all() and (y[:64, N:] == 0).all() and (y[64] == 5.0).all()
-    if score:
-        assert (diff[M:64, c0:c0 + N] == 0).all()                     # rows >= M: written as zero
-        assert (diff[:, :c0] == 77.0).all() and (diff[:, c0 + N:] == 77.0).all() and (diff[64:] == 77.0).all()
-        assert (rowsq[-1] == 55.0).all()
-        rs = rowsq[:-1].double().cpu().numpy()                        # [tiles][64]
-        assert (rs[:, M:] == 0).all()
-        d = np.zeros((64, Np))
-        d[:M, :N] = got
-        wgt = np.ones(Np) if cw is None else np.r_[cw.astype(np.float64), np.zeros(Np - N)]
-        want = ((d * d * wgt).reshape(64, Np // 16, 16).sum(-1)).T    # columns >= N: d = 0
-        assert (rs[N // 16 + 1:] == 0).all()
-        assert np.all(np.abs(rs - want) <= 8 * 2.0 ** -24 * want + 1e-300)
-    else:
-        assert (rowsq == 55.0).all() and (diff == 77.0).all()
-    assert e_new <= 2 * e_old
+    """The bars of tests/test_gpu_online.py::test_fc_rows16_against_fp64
+    (tests/online_fixture.py::check_fc_rows_against_fp64) on the 64-row layouts."""
+    check_fc_rows_against_fp64(64, M, N, K, dtype, variant)
 
 
 # ------------------------------------- 3. the whole pass vs the 16-row pass, bits
-class _Rig:
-    """Fixed buffers for raw mmad_ae_online_score (rows=16) / _score64 calls."""
-
-    def __init__(self, m, rows, canary=-7.0):
-        self.nat = nat = m._native
-        self.rows, self.canary = rows, canary
-        self.x = torch.zeros((rows, nat.enc_widths[0]), device="cuda")
-        self.out = torch.full((nat.n_enc + 4, rows), canary, device="cuda")
-        self.flags = torch.full((3, rows), 9, device="cuda", dtype=torch.uint8)
-        self.thr = torch.full((3,), float("nan"), device="cuda")
-        self.state = nat.online_state(rows)
-
-    def run(self, x, graph=False, start=0, end=None, fresh=False):
-        B = x.shape[0]
-        self.x[:B].copy_(x)
-        self.out.fill_(self.canary)
-        self.flags.fill_(9)
-        if fresh:
-            self.state = self.nat.online_state(self.rows)
-        self.nat.online_score(self.x, B, self.out, self.state, flags=self.flags, thresholds=self.thr,
-                              start=start, end=end, graph=graph, rows=self.rows)
-        torch.cuda.synchronize()
-        return self.out.clone(), self.flags.clone()
-
-
 def _by_groups_of_16(rig16, x, **kw):
     """The 16-row pass over x's windows in groups of 16: (out [n+4, B], flags [3, B])."""
     outs, fls = [], []
