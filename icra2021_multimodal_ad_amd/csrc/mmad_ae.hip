@@ -35,16 +35,53 @@ static unsigned ev_flags(int sysfence) {
                   : (unsigned)(hipEventDisableTiming | hipEventDisableSystemFence);
 }
 
-// can the dispatcher choose a split-K factor > 1 for this handle's GEMMs?
-// (any dtype: a forced override, knob 4; bf16: the dW rule, when a dW
-// override or the dW split target is set; fp32: knob 32's dW rule -- by
-// default nothing splits)
+// can the dispatcher choose a split-K factor > 1 for the GEMMs of a handle of
+// this dtype under the knobs as they stand?  Asked once per handle, by
+// schedule_from_knobs.  (any dtype: a forced override, knob 4; bf16: the dW
+// rule, when a dW override or the dW split target is set; fp32: knob 32's dW
+// rule, on by default from 2048 rows)
 static bool splitk_possible(int dtype) {
   const int o = mmad_splitk_override();
   if (o > 1) return true;
   if (o == 1) return false;
   if (dtype != MMAD_BF16) return mmad_splitk_dw_f32_blocks() > 0;
   return mmad_splitk_dw_override() > 1 || mmad_splitk_dw_blocks() > 0;
+}
+
+// The schedule of a new handle, from the tune table as it stands now
+// (include/mmad.h knobs 14-31, 33-35; 4 / 9 / 10 / 32 for the split-K slabs).
+// The only place in the executor that reads a schedule knob.
+static AeSchedule schedule_from_knobs(int dtype) {
+  AeSchedule s;
+  const int m = mmad_knob(KNOB_BN_MODE);
+  s.fold = dtype == MMAD_BF16;
+  s.bn_mode = dtype == MMAD_BF16 ? 2 : 0;
+  if (m >= 0 && m <= 2) {
+    s.bn_mode = m;
+    s.fold = m != 0 && dtype == MMAD_BF16;   // fold: mode 1, mode 2's fallback
+  }
+  s.bn_mode_bwd = mmad_knob(KNOB_BN_MODE_BWD);
+  s.bn_fused_rows = mmad_knob(KNOB_BN_FUSED_ROWS);
+  s.dw_main = mmad_knob(KNOB_DW_MAIN);
+  s.pair_rows = mmad_knob(KNOB_PAIR_ROWS);
+  s.dw_main_ping = mmad_knob(KNOB_DW_MAIN_PING);
+  s.ev_every = mmad_knob(KNOB_EV_EVERY);
+  s.ev_on_kernel = mmad_knob(KNOB_EV_ON_KERNEL);
+  s.loss_side = mmad_knob(KNOB_LOSS_SIDE);
+  s.dp_small_at = mmad_knob(KNOB_DP_SMALL_AT);
+  s.keep_grads = mmad_knob(KNOB_KEEP_GRADS);
+  s.side_prio_hi = mmad_knob(KNOB_SIDE_PRIO);
+  s.side_cu_held = mmad_knob(KNOB_SIDE_CU_HELD);
+  s.dp_shard = mmad_knob(KNOB_DP_SHARD);
+  s.side_hold = mmad_knob(KNOB_SIDE_HOLD);
+  s.dw_late = mmad_knob(KNOB_DW_LATE);
+  s.fork_on_kernel = mmad_knob(KNOB_FORK_ON_KERNEL);
+  s.fork_pair_below = mmad_knob(KNOB_FORK_PAIR_BELOW);
+  s.dp_bucket_mib = std::max(0, mmad_knob(KNOB_DP_BUCKET_MIB));
+  s.dp_fork_rows = mmad_knob(KNOB_DP_FORK_ROWS);
+  s.ev_flags_ = ev_flags(mmad_knob(KNOB_EVENT_SYSFENCE));
+  s.splitk_ws = splitk_possible(dtype);
+  return s;
 }
 
 void mmad_ae_impl::carve(const mmad_ae* h, int B, int k, char* base, AeWS& w) {
@@ -98,13 +135,12 @@ void mmad_ae_impl::carve(const mmad_ae* h, int B, int k, char* base, AeWS& w) {
   w.dyn_dev = (MmadDyn*)take(sizeof(MmadDyn));
   w.dyn = nullptr;
   {
-    // the split-K partial slabs (54.5 MB per stream) only when the current
-    // knobs let the dispatcher split one of this handle's GEMMs; without a
-    // slab it never splits.  Sized per call from the knobs in force, so a
-    // later override grows the workspace the next size query reports (and a
-    // caller that skipped the query gets "workspace too small", not an overrun)
+    // the split-K partial slabs (54.5 MB per stream) only for a handle whose
+    // schedule holds them (AeSchedule::splitk_ws, fixed at create: every
+    // offset below is the same in every call on the handle); without a slab
+    // the dispatcher never splits
     size_t slab = 0, ctl = 0;
-    if (splitk_possible(h->dtype)) mmad_gemm_splitk_bytes(0, 0, &slab, &ctl);
+    if (h->sched.splitk_ws) mmad_gemm_splitk_bytes(0, 0, &slab, &ctl);
     w.sk_slab[0] = slab ? (float*)take((int64_t)slab) : nullptr;
     w.sk_slab[1] = slab ? (float*)take((int64_t)slab) : nullptr;
   }
@@ -176,36 +212,7 @@ int mmad_ae_create(mmad_ae** out, int dtype, int n_enc, const int* enc_widths, i
   h->slope = slope;
   h->bn_eps = bn_eps;
   h->bn_mom = bn_momentum;
-  {
-    // the schedule knobs (include/mmad.h 16-27), read once for this handle
-    const int m = mmad_knob(16);
-    h->fold = dtype == MMAD_BF16;
-    h->bn_mode = dtype == MMAD_BF16 ? 2 : 0;
-    if (m >= 0 && m <= 2) {
-      h->bn_mode = m;
-      h->fold = m != 0 && dtype == MMAD_BF16;   // fold: mode 1, mode 2's fallback
-    }
-    h->bn_mode_bwd = mmad_knob(17);
-    h->bn_fused_rows = mmad_knob(18);
-    h->dw_main = mmad_knob(19);
-    h->pair_rows = mmad_knob(20);
-    h->dw_main_ping = mmad_knob(21);
-    h->ev_every = mmad_knob(22);
-    h->ev_on_kernel = mmad_knob(31);
-    h->loss_side = mmad_knob(23);
-    h->dp_small_at = mmad_knob(24);
-    h->keep_grads = mmad_knob(25);
-    h->side_prio_hi = mmad_knob(26);
-    h->side_cu_held = mmad_knob(15);
-    h->dp_shard = mmad_knob(28);
-    h->side_hold = mmad_knob(29);
-    h->dw_late = mmad_knob(33);
-    h->fork_on_kernel = mmad_knob(34);
-    h->fork_pair_below = mmad_knob(35);
-    h->dp_bucket_mib = mmad_knob(30) < 0 ? 0 : mmad_knob(30);
-    h->dp_fork_rows = mmad_knob(14);
-    h->ev_flags_ = ev_flags(mmad_knob(27));
-  }
+  h->sched = schedule_from_knobs(dtype);
   for (int side = 0; side < 2; ++side) {
     const int n = side == 0 ? n_enc : n_dec;
     const int* wd = side == 0 ? enc_widths : dec_widths;
@@ -281,7 +288,7 @@ int mmad_ae_bind(mmad_ae* h, float* params, float* grads, float* adam_m, float* 
     int least = 0, greatest = 0;
     MMAD_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
     // (knob 26: the highest priority instead, for schedule sweeps)
-    if (h->side_cu_held > 0) {
+    if (h->sched.side_cu_held > 0) {
       // schedule study: the side stream's dW + Adam GEMMs kept off side_cu_held
       // CUs so the bwd-data / BN-apply chain always has CUs of its own.  The
       // masked stream is created blocking at the default priority (the API
@@ -290,7 +297,7 @@ int mmad_ae_bind(mmad_ae* h, float* params, float* grads, float* adam_m, float* 
       int dev = 0, ncu = 0;
       MMAD_HIP_CHECK(hipGetDevice(&dev));
       MMAD_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-      const int held = std::min(h->side_cu_held, ncu - 1), stride = std::max(1, ncu / std::max(1, held));
+      const int held = std::min(h->sched.side_cu_held, ncu - 1), stride = std::max(1, ncu / std::max(1, held));
       std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
       for (int i = 0, n_held = 0; i < ncu; ++i) {
         const bool hold = n_held < held && i % stride == stride - 1;
@@ -300,18 +307,18 @@ int mmad_ae_bind(mmad_ae* h, float* params, float* grads, float* adam_m, float* 
       MMAD_HIP_CHECK(hipExtStreamCreateWithCUMask(&h->side, (uint32_t)mask.size(), mask.data()));
     } else {
       MMAD_HIP_CHECK(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking,
-                                                 h->side_prio_hi ? greatest : least));
+                                                 h->sched.side_prio_hi ? greatest : least));
     }
     const size_t n = h->L.size();
     h->ev_fork.resize(n);
     h->ev_data.resize(n);
     for (size_t i = 0; i < n; ++i) {
-      MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_fork[i], h->ev_flags_));
-      MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_data[i], h->ev_flags_));
+      MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_fork[i], h->sched.ev_flags_));
+      MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_data[i], h->sched.ev_flags_));
     }
-    MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_join, h->ev_flags_));
-    MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_hold, h->ev_flags_));
-    MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_loss, h->ev_flags_));
+    MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_join, h->sched.ev_flags_));
+    MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_hold, h->sched.ev_flags_));
+    MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_loss, h->sched.ev_flags_));
   }
   return MMAD_OK;
 }
@@ -390,14 +397,15 @@ int mmad_ae_impl::prepare_ws(const mmad_ae* h, int B, int k, void* ws, int64_t w
   // split-K arrival counters / flags must be zero before a split GEMM runs;
   // every split GEMM leaves them zero again, so a workspace is zeroed once
   // when this handle first sees it (and mmad_ae_status re-zeroes after a
-  // timed-out combine); only when a split can be chosen at all
-  w.bn_mode = h->bn_mode;
+  // timed-out combine); only on a handle that holds the split-K slabs or
+  // fuses BN -- no other handle's kernels read the words
+  w.bn_mode = h->sched.bn_mode;
   w.ping = false;
-  w.dw_main = h->dw_main;
-  if (w.bn_mode == 2 && w.Mpd > h->bn_fused_rows) w.bn_mode = h->fold ? 1 : 0;
-  if (w.bn_mode == 1 && !h->fold) w.bn_mode = 0;
-  w.bn_mode_bwd = (h->bn_mode_bwd >= 0 && h->fold) ? h->bn_mode_bwd : w.bn_mode;
-  if ((splitk_possible(h->dtype) || h->bn_mode == 2 || h->bn_mode_bwd == 2) &&
+  w.dw_main = h->sched.dw_main;
+  if (w.bn_mode == 2 && w.Mpd > h->sched.bn_fused_rows) w.bn_mode = h->sched.fold ? 1 : 0;
+  if (w.bn_mode == 1 && !h->sched.fold) w.bn_mode = 0;
+  w.bn_mode_bwd = (h->sched.bn_mode_bwd >= 0 && h->sched.fold) ? h->sched.bn_mode_bwd : w.bn_mode;
+  if ((h->sched.splitk_ws || h->sched.bn_mode == 2 || h->sched.bn_mode_bwd == 2) &&
       ws != h->ws_zeroed) {
     MMAD_HIP_CHECK(hipMemsetAsync(w.sk_ctl[0], 0, w.sk_ctl_bytes, st));
     const_cast<mmad_ae*>(h)->ws_zeroed = ws;
@@ -426,7 +434,7 @@ struct DpBucket {
 static void dp_plan(const mmad_ae* h, std::vector<DpBucket>& out) {
   out.clear();
   const int nL = (int)h->L.size();
-  const int64_t min_n = (int64_t)h->dp_bucket_mib * (1 << 20) / 4;
+  const int64_t min_n = (int64_t)h->sched.dp_bucket_mib * (1 << 20) / 4;
   int hi = nL - 1;
   int64_t acc = 0;
   for (int l = nL - 1; l >= 0; --l) {
@@ -746,12 +754,12 @@ struct BwdRun {
   // ping-pong shadows (bf16): the fused Adam of dW_l writes the other shadow,
   // so dW_l may start as soon as dz_l is complete
   bool ping(int l) const { return fused() && w.ping && l >= w.dw_main; }
-  bool late(int l) const { return ping(l) && l >= nL - h->dw_late; }
+  bool late(int l) const { return ping(l) && l >= nL - h->sched.dw_late; }
   // does layer l's side-stream dW (ping) get a fork event of its own (knob 35)?
   bool fork_ev(int l) const {
     // a group forks once, at its lowest member
     if (grp[l] >= 0) return l == 0 || grp[l - 1] != grp[l];
-    const int P = h->fork_pair_below;
+    const int P = h->sched.fork_pair_below;
     if (P <= 0 || l > P || l == w.dw_main) return true;
     return (P - l) % 2 == 1;
   }
@@ -769,7 +777,7 @@ struct BwdRun {
   bool needs_data_ev(int l) const {
     if (dp()) return closes_bucket(l) != nullptr;
     if (!fused() || ping(l) || l < w.dw_main) return false;
-    return h->ev_every <= 1 || l == w.dw_main || (l - w.dw_main) % h->ev_every == 0;
+    return h->sched.ev_every <= 1 || l == w.dw_main || (l - w.dw_main) % h->sched.ev_every == 0;
   }
 };
 
@@ -811,8 +819,8 @@ static PendingDW make_dw(const BwdRun& r, int l) {
     e.ad_v = h->v + a.w_off;
     e.ad_shadow = adam_shadow(h, a, w.ping);
     // the gradient is consumed by the fused Adam in registers; materialise
-    // it only when asked (h->keep_grads)
-    e.dw_nostore = h->keep_grads ? 0 : 1;
+    // it only when asked (h->sched.keep_grads)
+    e.dw_nostore = h->sched.keep_grads ? 0 : 1;
     e.ad_w1 = r.adam->w1;
     e.ad_w2 = r.adam->w2;
     e.ad_eps = r.adam->eps;
@@ -920,7 +928,7 @@ static int bwd_data_step(BwdRun& r, int l, hipEvent_t done_ev, hipEvent_t fork_b
   // dz_{l-1} comes from the BN apply launch; across the VIB hop, from the
   // reparameterisation backward, and neither event rides a launch
   const bool apply = !hop && p.bn && !ps.bwd_fused;
-  if (!hop && done_ev && h->ev_on_kernel && !h->capturing) {
+  if (!hop && done_ev && h->sched.ev_on_kernel && !h->capturing) {
     ep.done_ev = done_ev;
     placed->done = true;
   } else if (!hop && fork_below && !apply) {
@@ -974,7 +982,7 @@ static int dp_before(BwdRun& r, int l) {
   // from dp_fork_rows rows the step is GPU-bound: a side-stream bucket's dW
   // GEMMs then start at their own dz (one fork each) instead of queueing
   // until the bucket's lowest layer
-  const bool each = h->dp_fork_rows > 0 && prows_of(r.w, h->L[l]) >= h->dp_fork_rows && cur && !on_main;
+  const bool each = h->sched.dp_fork_rows > 0 && prows_of(r.w, h->L[l]) >= h->sched.dp_fork_rows && cur && !on_main;
   // (a bucket whose upper layers were below the row threshold: their dW GEMMs
   // go first, so the bucket's event below covers them too)
   r.pending.push_back(make_dw(r, l));
@@ -1018,7 +1026,7 @@ static int exchange_bucket(BwdRun& r, const DpBucket& bk, int l) {
   const int nr = mmad_comm_size(h->comm) > 0 ? mmad_comm_size(h->comm) : 1;
   MMAD_HIP_CHECK(hipStreamWaitEvent(cs, h->ev_dw[l], 0));
   const int64_t n = bk.n, boff = bk.off;
-  if (h->dp_shard && n % nr == 0 && (n / nr) % 4 == 0) {
+  if (h->sched.dp_shard && n % nr == 0 && (n / nr) % 4 == 0) {
     // ZeRO-1 form: reduce-scatter, Adam on this rank's shard, all-gather
     // of the updated weights the next step reads (bf16 shadow / fp32 p)
     const int64_t cnt = n / nr, off = boff + (int64_t)mmad_comm_rank(h->comm) * cnt;
@@ -1055,7 +1063,7 @@ static int exchange_bucket(BwdRun& r, const DpBucket& bk, int l) {
 // the chain keeps overlapping it.
 static void fused_plan_groups(BwdRun& r) {
   mmad_ae* h = r.h;
-  if (!r.w.ping || h->capturing || h->side_hold || h->dw_group_blocks == 0) return;
+  if (!r.w.ping || h->capturing || h->sched.side_hold || h->dw_group_blocks == 0) return;
   std::vector<int> np(r.nL), kp(r.nL), rows(r.nL);
   for (int l = 0; l < r.nL; ++l) {
     np[l] = h->L[l].Np;
@@ -1063,7 +1071,7 @@ static void fused_plan_groups(BwdRun& r) {
     rows[l] = prows_of(r.w, h->L[l]);
   }
   const int budget = h->dw_group_blocks < 0 ? mmad_gemm_group_capacity(h->dtype) : h->dw_group_blocks;
-  mmad_dw_group_plan(r.nL, np.data(), kp.data(), rows.data(), r.w.dw_main, r.nL - h->dw_late, budget,
+  mmad_dw_group_plan(r.nL, np.data(), kp.data(), rows.data(), r.w.dw_main, r.nL - h->sched.dw_late, budget,
                      h->dw_group_members, r.grp.data());
 }
 static int fused_before(BwdRun& r, int l) {
@@ -1084,7 +1092,7 @@ static int fused_after(BwdRun& r, int l) {
   }
   // deferred dW GEMMs go out ahead of this one
   r.pending.push_back(q);
-  if (h->side_hold) return MMAD_OK;   // all of them behind the chain (run_backward)
+  if (h->sched.side_hold) return MMAD_OK;   // all of them behind the chain (run_backward)
   if (r.ping(l)) {
     // no fork of its own: issued with the next lower layer's dW
     if (!r.late(l) && !r.fork_ev(l)) return MMAD_OK;
@@ -1105,12 +1113,12 @@ static int run_backward(mmad_ae* h, AeWS& w, bool from_mse, float beta_kl, const
                         hipStream_t st, float* dp_loss = nullptr, bool side_after_mse = false) {
   const int nL = (int)h->L.size();
   BwdRun r{h, w, st, h->side, adam, from_mse, side_after_mse, beta_kl, dp_loss, nL,
-           h->fork_on_kernel && !h->capturing};
+           h->sched.fork_on_kernel && !h->capturing};
   r.fork_done.assign(nL, 0);
   r.grp.assign(nL, -1);
   if (r.dp()) dp_plan(h, r.plan);
   if (r.fused()) fused_plan_groups(r);
-  const int small_at = nL > h->dp_small_at ? h->dp_small_at : 0;
+  const int small_at = nL > h->sched.dp_small_at ? h->sched.dp_small_at : 0;
   for (int l = nL - 1; l >= 0; --l) {
     // DP and plain issue dW_l before the bwd-data of l, fused after it
     RET_IF(!adam ? plain_before(r, l) : r.dp() ? dp_before(r, l) : fused_before(r, l));
@@ -1128,7 +1136,7 @@ static int run_backward(mmad_ae* h, AeWS& w, bool from_mse, float beta_kl, const
     if (r.fused()) RET_IF(fused_after(r, l));
     if (const DpBucket* bk = r.closes_bucket(l)) RET_IF(exchange_bucket(r, *bk, l));
   }
-  if (h->side_hold && !r.pending.empty()) {
+  if (h->sched.side_hold && !r.pending.empty()) {
     RET_IF(hand_off(h->ev_hold, st, r.side));
     RET_IF(flush(r, r.side));
   }
@@ -1211,12 +1219,12 @@ int mmad_ae_train_step(mmad_ae* h, const float* x, int ld_x, int B, int k, const
   hipStream_t st = (hipStream_t)stream;
   const AdamHyper ah = adam_hyper(lr, beta1, beta2, adam_eps, step);
   // ping-pong schedule (bf16 with a shadow pair, large calls, single process)
-  w.ping = h->shadow_alt && !h->comm && !h->capturing && w.Mpe >= h->pair_rows;
-  if (w.ping) w.dw_main = h->dw_main_ping;
+  w.ping = h->shadow_alt && !h->comm && !h->capturing && w.Mpe >= h->sched.pair_rows;
+  if (w.ping) w.dw_main = h->sched.dw_main_ping;
   // the side stream's loss reduction waits on the MSE launch's own completion
-  const bool loss_ev_on_kernel = !h->comm && h->loss_side && h->ev_on_kernel && !h->capturing;
+  const bool loss_ev_on_kernel = !h->comm && h->sched.loss_side && h->sched.ev_on_kernel && !h->capturing;
   RET_IF(run_forward(h, w, x, ld_x, 0, eps, seed, offset, st, loss_ev_on_kernel ? h->ev_loss : nullptr));
-  if (!h->comm && !h->loss_side) {
+  if (!h->comm && !h->sched.loss_side) {
     RET_IF(run_backward(h, w, true, beta_kl, &ah, st));
     RET_IF(finish_reductions(h, w, false, true, beta_kl, loss_out, st));
     if (w.ping) std::swap(h->shadow, h->shadow_alt);
@@ -1262,7 +1270,7 @@ int mmad_ae_train_step_graph(mmad_ae* h, const float* x, int ld_x, int B, int k,
   if (!h->dyn_host) {
     MMAD_HIP_CHECK(hipHostMalloc((void**)&h->dyn_host, sizeof(MmadDyn) * mmad_ae::kDynSlots,
                                  hipHostMallocDefault));
-    for (auto& e : h->dyn_ev) MMAD_HIP_CHECK(hipEventCreateWithFlags(&e, h->ev_flags_));
+    for (auto& e : h->dyn_ev) MMAD_HIP_CHECK(hipEventCreateWithFlags(&e, h->sched.ev_flags_));
   }
   const int slot = h->dyn_next;
   h->dyn_next = (slot + 1) % mmad_ae::kDynSlots;
@@ -1279,7 +1287,7 @@ int mmad_ae_train_step_graph(mmad_ae* h, const float* x, int ld_x, int B, int k,
   MMAD_HIP_CHECK(hipEventRecord(h->dyn_ev[slot], st));
   h->dyn_used[slot] = true;
   const int xvec = ((uintptr_t)x % 16 == 0 && ld_x % 4 == 0) ? 1 : 0;
-  const TrainKey key{B, k, ld_x, xvec, eps != nullptr, h->dw_main, h->ev_every, h->keep_grads, ws,
+  const TrainKey key{B, k, ld_x, xvec, eps != nullptr, h->sched.dw_main, h->sched.ev_every, h->sched.keep_grads, ws,
                      h->shadow, beta_kl, beta1, beta2, adam_eps};
   if (hipGraphExec_t hit = h->tgraphs.find(key)) {
     MMAD_HIP_CHECK(hipGraphLaunch(hit, st));
@@ -1325,7 +1333,7 @@ int mmad_ae_set_comm(mmad_ae* h, mmad_comm* c) {
     h->ev_dw.resize(h->L.size());
     for (auto& e : h->ev_dw) MMAD_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_small, hipEventDisableTiming));
-    MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_cdone, h->ev_flags_));
+    MMAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_cdone, h->sched.ev_flags_));
   }
   h->comm = c;
   return MMAD_OK;
@@ -1463,16 +1471,16 @@ int mmad_ae_forward(mmad_ae* h, const float* x, int ld_x, int B, int train_bn, f
 
 int mmad_ae_status(mmad_ae* h, void* ws, int64_t ws_bytes, void* stream) {
   MMAD_CHECK_ARG(h, "ae_status: null handle");
-  // no split-K GEMM / fused-BN barrier can have run unless the dtype /
-  // override / BN mode allows one
-  if ((!splitk_possible(h->dtype) && h->bn_mode != 2 && h->bn_mode_bwd != 2) || !ws)
+  // no split-K GEMM / fused-BN barrier can have run unless the handle's
+  // schedule holds the split-K slabs / a fused BN mode
+  if ((!h->sched.splitk_ws && h->sched.bn_mode != 2 && h->sched.bn_mode_bwd != 2) || !ws)
     return MMAD_OK;
   AeWS w;
   carve(h, 1, 1, (char*)ws, w);
   MMAD_CHECK_ARG(ws_bytes >= w.bytes, "ae_status: workspace too small");
   for (int r = 0; r < 2; ++r)
     RET_IF(mmad_gemm_read_status(w.sk_ctl[r], (hipStream_t)stream, "ae_status"));
-  if ((h->bn_mode == 2 || h->bn_mode_bwd == 2) && w.bn_err) {
+  if ((h->sched.bn_mode == 2 || h->sched.bn_mode_bwd == 2) && w.bn_err) {
     unsigned word = 0;
     MMAD_HIP_CHECK(hipMemcpyAsync(&word, w.bn_err, sizeof(word), hipMemcpyDeviceToHost, (hipStream_t)stream));
     MMAD_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));

@@ -109,45 +109,17 @@ struct TrainKey {
   }
 };
 
-}  // namespace mmad_ae_impl
-
-struct mmad_ae {
-  int dtype, n_enc, n_dec, vib, btl;
-  float slope, bn_eps, bn_mom;
-  std::vector<mmad_ae_impl::AeLayer> L;
-  int64_t n_params, n_weight, n_bn;
-  float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *running = nullptr;
-  void* shadow = nullptr;
-  // bf16 ping-pong: the fused step's Adam writes the new weights into
-  // shadow_alt while this step's backward still reads shadow, then the two
-  // swap; so a dW GEMM need not wait for its layer's bwd-data GEMM
-  void* shadow_alt = nullptr;
-  // split-bf16 scoring (mmad_ae_set_score_planes, F32 handles): bf16
-  // [2][n_weight] weight planes; the eval forward / score GEMMs then run as
-  // MMAD_BF16X3.  planes_stale: the fp32 weights were (or may have been)
-  // written since the last split; the scoring entry points re-split first
-  void* planes = nullptr;
-  bool planes_stale = true;
-  // streamed NAP (mmad_ae_set_nap): the fit of the concatenated diffs of the
-  // diff layers [start, end) (0 = x_hat - x, 1 + e = encoder layer e), all
-  // caller-owned.  dtype: the NAP GEMM's (MMAD_F32: fp32 operand written
-  // through the score GEMMs' diff output; MMAD_BF16X3: plane operand written
-  // through their diff-plane output, vt split into vt_planes at attach)
-  struct NapFit {
-    bool on = false;
-    int start = 0, end = 0, K = 0, Kp = 0, R = 0, Rp = 0, dtype = MMAD_F32;
-    const float *vt = nullptr, *bias = nullptr, *w = nullptr;
-    void* vt_planes = nullptr;
-  } nap;
-  // side stream + events for the dW / Adam overlap (created at bind time)
-  hipStream_t side = nullptr;
-  std::vector<hipEvent_t> ev_fork, ev_data;
-  hipEvent_t ev_join = nullptr;
-  hipEvent_t ev_loss = nullptr;   // fused step: forward done -> the loss reduction on the side stream
-  // the schedule, copied from the tune table at create (include/mmad.h knobs
-  // 16-27): one schedule per handle, whatever the table says later
-  unsigned ev_flags_ = 0;
-  int loss_side = 1;      // knob 23: reduce the loss on the side stream after the forward
+// The schedule of one executor handle: built once from the tune table by
+// schedule_from_knobs (mmad_ae.hip) when the handle is created and constant
+// from then on -- one schedule per handle, whatever the table says later.
+// Nothing else in the executor reads a schedule knob.  (The grouped-dW budget,
+// mmad_ae::dw_group_blocks / dw_group_members, is the one schedule choice that
+// can change after create, through mmad_ae_set_dw_group; it is not in here.)
+// AeWS carries each call's resolution of these (bn_mode, bn_mode_bwd, dw_main,
+// ping).
+struct AeSchedule {
+  unsigned ev_flags_ = 0;   // flags of the executor's events (knob 27; ev_flags, mmad_ae.hip)
+  int loss_side = 1;     // knob 23: reduce the loss on the side stream after the forward
   int side_prio_hi = 0;   // knob 26
   // knob 15: > 0 = the side stream is created behind a CU mask that leaves
   // this many CUs (evenly spaced over the mask) to the main stream alone
@@ -156,9 +128,7 @@ struct mmad_ae {
   // goes on the comm stream right after the bwd-data GEMM of this layer
   // (ahead of this layer's and the lower layers' weight buckets); knob 24
   int dp_small_at = 1;
-  // data-parallel step: sharded weight buckets (knob 28); master_stale: the
-  // bf16 model's fp32 master weights / every model's Adam moments are
-  // current only on their owning rank since the last mmad_ae_dp_sync_master
+  // data-parallel step: sharded weight buckets (knob 28)
   int dp_shard = 1;
   // data-parallel step: consecutive layers' weight gradients (backward
   // order) share one exchange bucket until it holds at least dp_bucket_mib
@@ -168,21 +138,6 @@ struct mmad_ae {
   // is issued as soon as its own dz is complete instead of with its bucket's
   // closing layer (knob 14; 0 = one fork per bucket)
   int dp_fork_rows = 1024;
-  bool master_stale = false;
-  int mse_tiles = 0;   // loss partials written by the last MSE GEMM
-  // data parallelism: RCCL communicator (not owned), its stream and events
-  mmad_comm* comm = nullptr;
-  hipStream_t cstream = nullptr;
-  std::vector<hipEvent_t> ev_dw;
-  // torch-exchange data parallelism (mmad_ae_dw_events): the forward+backward
-  // without Adam records ev_xdw[l] after dW_l and ev_xdata[l] after bwd-data of
-  // l.  System-scope fences (unlike the executor's own events): the exchange
-  // may read the gradients with a copy engine, which does not see the L2
-  bool dw_events = false;
-  std::vector<hipEvent_t> ev_xdw, ev_xdata;
-  // optional bf16 gradient exchange (mmad_ae_set_grad_bf16): n_weight bf16
-  void* grad_bf16 = nullptr;
-  hipEvent_t ev_small = nullptr, ev_cdone = nullptr;
   // schedule study (knob 29): every side-stream dW + Adam GEMM held until the
   // main stream has enqueued the whole bwd-data chain (ev_hold), to separate
   // the chain's in-step contention from its barrier costs
@@ -204,16 +159,6 @@ struct mmad_ae {
   // by more than a layer anyway, each fork saved is a ~5-us hold on the
   // main stream; 0 = every layer forks)
   int fork_pair_below = 0;
-  // ping-pong steps (mmad_ae_set_dw_group): consecutive side-stream layers
-  // whose dW + Adam GEMM takes the 64x64 tile are issued as ONE grouped launch
-  // (mmad_gemm_dispatch_group) at the lowest member's fork -- at 4096 rows
-  // each of the narrow layers' launches is one block's 64-stage K loop,
-  // 23-25 us for 16 to 135 blocks, and they ran back to back.  blocks = the
-  // group's budget of padded blocks (0 = off: every dW its own launch; < 0 =
-  // one resident round of the kernel), members = at most this many per group
-  int dw_group_blocks = MMAD_DW_GROUP_BLOCKS_DEFAULT;
-  int dw_group_members = MMAD_GEMM_GROUP_MAX;
-  hipEvent_t ev_hold = nullptr;
   // fused step: dW GEMMs of layers < dw_main run on the caller's stream
   // (knob 19; tools/sched_sweep.py: 0.499 ms (2) vs 0.512 (1) vs 0.523 (3));
   // keep_grads (knob 25): also write dW to the grads buffer
@@ -257,6 +202,81 @@ struct mmad_ae {
   // the main stream's hand-off events (bwd-data -> side-stream dW, MSE ->
   // side-stream loss) completed by the GEMM launch itself (knob 31)
   int ev_on_kernel = 1;
+  // the workspace holds the two split-K partial slabs (54.5 MB per stream):
+  // the dispatcher could choose a split factor > 1 for one of this handle's
+  // GEMMs under the knobs in force at create (4; bf16: 9, 10; fp32: 32).
+  // Without the slabs no GEMM of the handle ever splits, with them the
+  // dispatcher follows the current knobs; either way the workspace layout
+  // depends on (handle, B, k) only
+  bool splitk_ws = false;
+};
+
+}  // namespace mmad_ae_impl
+
+struct mmad_ae {
+  int dtype, n_enc, n_dec, vib, btl;
+  float slope, bn_eps, bn_mom;
+  std::vector<mmad_ae_impl::AeLayer> L;
+  int64_t n_params, n_weight, n_bn;
+  float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *running = nullptr;
+  void* shadow = nullptr;
+  // bf16 ping-pong: the fused step's Adam writes the new weights into
+  // shadow_alt while this step's backward still reads shadow, then the two
+  // swap; so a dW GEMM need not wait for its layer's bwd-data GEMM
+  void* shadow_alt = nullptr;
+  // split-bf16 scoring (mmad_ae_set_score_planes, F32 handles): bf16
+  // [2][n_weight] weight planes; the eval forward / score GEMMs then run as
+  // MMAD_BF16X3.  planes_stale: the fp32 weights were (or may have been)
+  // written since the last split; the scoring entry points re-split first
+  void* planes = nullptr;
+  bool planes_stale = true;
+  // streamed NAP (mmad_ae_set_nap): the fit of the concatenated diffs of the
+  // diff layers [start, end) (0 = x_hat - x, 1 + e = encoder layer e), all
+  // caller-owned.  dtype: the NAP GEMM's (MMAD_F32: fp32 operand written
+  // through the score GEMMs' diff output; MMAD_BF16X3: plane operand written
+  // through their diff-plane output, vt split into vt_planes at attach)
+  struct NapFit {
+    bool on = false;
+    int start = 0, end = 0, K = 0, Kp = 0, R = 0, Rp = 0, dtype = MMAD_F32;
+    const float *vt = nullptr, *bias = nullptr, *w = nullptr;
+    void* vt_planes = nullptr;
+  } nap;
+  // side stream + events for the dW / Adam overlap (created at bind time)
+  hipStream_t side = nullptr;
+  std::vector<hipEvent_t> ev_fork, ev_data;
+  hipEvent_t ev_join = nullptr;
+  hipEvent_t ev_loss = nullptr;   // fused step: forward done -> the loss reduction on the side stream
+  // the schedule (tune-table knobs 14-31, 33-35 and the split-K slab decision),
+  // fixed at create
+  mmad_ae_impl::AeSchedule sched;
+  // sharded data-parallel steps (sched.dp_shard): the bf16 model's fp32 master
+  // weights / every model's Adam moments are current only on their owning
+  // rank since the last mmad_ae_dp_sync_master
+  bool master_stale = false;
+  int mse_tiles = 0;   // loss partials written by the last MSE GEMM
+  // data parallelism: RCCL communicator (not owned), its stream and events
+  mmad_comm* comm = nullptr;
+  hipStream_t cstream = nullptr;
+  std::vector<hipEvent_t> ev_dw;
+  // torch-exchange data parallelism (mmad_ae_dw_events): the forward+backward
+  // without Adam records ev_xdw[l] after dW_l and ev_xdata[l] after bwd-data of
+  // l.  System-scope fences (unlike the executor's own events): the exchange
+  // may read the gradients with a copy engine, which does not see the L2
+  bool dw_events = false;
+  std::vector<hipEvent_t> ev_xdw, ev_xdata;
+  // optional bf16 gradient exchange (mmad_ae_set_grad_bf16): n_weight bf16
+  void* grad_bf16 = nullptr;
+  hipEvent_t ev_small = nullptr, ev_cdone = nullptr;
+  hipEvent_t ev_hold = nullptr;   // sched.side_hold: the bwd-data chain is enqueued
+  // ping-pong steps (mmad_ae_set_dw_group): consecutive side-stream layers
+  // whose dW + Adam GEMM takes the 64x64 tile are issued as ONE grouped launch
+  // (mmad_gemm_dispatch_group) at the lowest member's fork -- at 4096 rows
+  // each of the narrow layers' launches is one block's 64-stage K loop,
+  // 23-25 us for 16 to 135 blocks, and they ran back to back.  blocks = the
+  // group's budget of padded blocks (0 = off: every dW its own launch; < 0 =
+  // one resident round of the kernel), members = at most this many per group
+  int dw_group_blocks = MMAD_DW_GROUP_BLOCKS_DEFAULT;
+  int dw_group_members = MMAD_GEMM_GROUP_MAX;
   // hipGraph cache for mmad_ae_score_stream: one captured graph per
   // (input, output, workspace, N, batch) pass, replayed with one launch
   mmad_ae_impl::GraphCache<mmad_ae_impl::ScoreKey> graphs{8};

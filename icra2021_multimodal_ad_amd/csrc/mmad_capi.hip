@@ -31,9 +31,13 @@ int mmad_pad_granule(void) { return MMAD_PAD; }
 
 // Tuning knobs: ONE table, set only through mmad_tune_set (the library reads
 // no environment variables, so every rank of a job runs the same schedule
-// unless its code says otherwise).  GEMM knobs (0-11) are read per dispatch;
-// the executor's schedule knobs (14-31, 33-35) are copied into a handle when it is
-// created (mmad_ae_create), so a handle keeps one schedule for its lifetime.
+// unless its code says otherwise).  GEMM knobs (0-13, 32) are read per
+// dispatch; the executor's schedule knobs (14-31, 33-35) are copied into a
+// handle when it is created (mmad_ae_create: AeSchedule), so a handle keeps
+// one schedule for its lifetime -- including whether its workspace holds the
+// split-K slabs, decided then from knobs 4 / 9 / 10 / 32: a handle without
+// them never splits, whatever those knobs say later.  The slots are named by
+// enum MmadKnob (mmad_gemm.h); the numbers below are its values.
 namespace {
 int g_knob[MMAD_KNOB_COUNT] = {
     -1,    // 0  GEMM tile override (-1 = autotuned)
@@ -74,20 +78,20 @@ int g_knob[MMAD_KNOB_COUNT] = {
     0,     // 35 ping-pong: side dW forks in pairs from this layer down (0 = every layer)
 };
 }  // namespace
-int mmad_knob(int k) { return g_knob[k]; }
-int mmad_tile_override() { return g_knob[0]; }
-int mmad_group_override() { return g_knob[1]; }
-int mmad_autotune_enabled() { return g_knob[2]; }
-int mmad_dbg_override() { return g_knob[3]; }
-int mmad_persist_override() { return g_knob[12]; }
-int mmad_splitk_override() { return g_knob[4]; }
-int mmad_splitk_dw_override() { return g_knob[9]; }
+int mmad_knob(MmadKnob k) { return g_knob[k]; }
+int mmad_tile_override() { return g_knob[KNOB_TILE]; }
+int mmad_group_override() { return g_knob[KNOB_GROUP_M]; }
+int mmad_autotune_enabled() { return g_knob[KNOB_AUTOTUNE]; }
+int mmad_dbg_override() { return g_knob[KNOB_DBG]; }
+int mmad_persist_override() { return g_knob[KNOB_PERSIST]; }
+int mmad_splitk_override() { return g_knob[KNOB_SPLITK]; }
+int mmad_splitk_dw_override() { return g_knob[KNOB_SPLITK_DW]; }
 // dW split-K target blocks (0 = no split): 512 paid before the dW loop stopped
 // draining its LDS ring every K stage; since then no split measures faster
 // (VIB B=4096 0.991-0.996 vs 1.013 ms/step with the split tail off; r02ae_*)
-int mmad_splitk_dw_blocks() { return g_knob[10]; }
-int mmad_splitk_dw_min_stages() { return g_knob[11]; }
-int mmad_splitk_dw_f32_blocks() { return g_knob[32]; }
+int mmad_splitk_dw_blocks() { return g_knob[KNOB_SPLITK_DW_BLOCKS]; }
+int mmad_splitk_dw_min_stages() { return g_knob[KNOB_SPLITK_DW_MIN_STAGES]; }
+int mmad_splitk_dw_f32_blocks() { return g_knob[KNOB_SPLITK_DW_F32_BLOCKS]; }
 // tile for the dW GEMMs with the fused Adam epilogue (the autotuner times
 // them without Adam, which under-weights the epilogue's HBM traffic: it picks
 // 128x128 for the large layers, 208 blocks for 256 CUs).  Default (-2) = a
@@ -96,9 +100,9 @@ int mmad_splitk_dw_f32_blocks() { return g_knob[32]; }
 // everywhere (0.522 vs 0.529 ms/step, tools/tile_adam_sweep.py); B=4096:
 // 67 vs 87 us at 1658x2048, 63 vs 78 at 1268x1658, 64x64 better below
 // (profiles/r02j_splitk_dw4096_vib.log).
-int mmad_tile_adam_override() { return g_knob[5]; }
+int mmad_tile_adam_override() { return g_knob[KNOB_TILE_ADAM]; }
 int mmad_tile_adam_for(int Mp, int Np, int K) {
-  if (g_knob[5] != -2) return g_knob[5];
+  if (g_knob[KNOB_TILE_ADAM] != -2) return g_knob[KNOB_TILE_ADAM];
   return (K >= 2048 && (long)Mp * Np >= 1500000L) ? 0 : 3;
 }
 // tile of the Adam-fused dW GEMMs that run on the main stream at the end of
@@ -110,15 +114,15 @@ int mmad_tile_adam_for(int Mp, int Np, int K) {
 // the knob-5 tiles and 0.4372-0.4378 with the rule on three boxes,
 // profiles/r05h_main_tail_dw_tile_ab.txt, r05t_main_tail_dw_tile_ab.txt; at
 // 4096 rows knob 5's rule already picks 128x128 for these layers).
-int mmad_tile_adam_main_override() { return g_knob[8]; }
+int mmad_tile_adam_main_override() { return g_knob[KNOB_TILE_ADAM_MAIN]; }
 int mmad_tile_adam_main_for(int Mp, int Np, int K) {
-  if (g_knob[8] != -2) return g_knob[8];
+  if (g_knob[KNOB_TILE_ADAM_MAIN] != -2) return g_knob[KNOB_TILE_ADAM_MAIN];
   return (Mp / 128) * (Np / 128) >= 200 ? 0 : mmad_tile_adam_for(Mp, Np, K);
 }
 // per-epilogue tile overrides (-1 = autotuned): bwd-data GEMMs, forward GEMMs
 int mmad_tile_epi_override(int epi) {
-  if (epi == GEMM_EPI_BWD_DATA) return g_knob[6];
-  if (epi == GEMM_EPI_FWD || epi == GEMM_EPI_MSE) return g_knob[7];
+  if (epi == GEMM_EPI_BWD_DATA) return g_knob[KNOB_TILE_BWD_DATA];
+  if (epi == GEMM_EPI_FWD || epi == GEMM_EPI_MSE) return g_knob[KNOB_TILE_FWD];
   return -1;
 }
 

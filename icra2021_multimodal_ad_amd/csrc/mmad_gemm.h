@@ -145,7 +145,50 @@ struct GemmEpi {
   int lddp, dp_col;
 };
 
-int mmad_knob(int k);          // the tune table (mmad_tune_set)
+// The slots of the tune table (include/mmad.h; mmad_tune_set), spelled after
+// their _native.KNOB keys.  The numbers are the public ones and never move.
+enum MmadKnob {
+  KNOB_TILE = 0,
+  KNOB_GROUP_M = 1,
+  KNOB_AUTOTUNE = 2,
+  KNOB_DBG = 3,
+  KNOB_SPLITK = 4,
+  KNOB_TILE_ADAM = 5,
+  KNOB_TILE_BWD_DATA = 6,
+  KNOB_TILE_FWD = 7,
+  KNOB_TILE_ADAM_MAIN = 8,
+  KNOB_SPLITK_DW = 9,
+  KNOB_SPLITK_DW_BLOCKS = 10,
+  KNOB_SPLITK_DW_MIN_STAGES = 11,
+  KNOB_PERSIST = 12,
+  KNOB_BN_APPLY_RB = 13,
+  KNOB_DP_FORK_ROWS = 14,
+  KNOB_SIDE_CU_HELD = 15,
+  KNOB_BN_MODE = 16,
+  KNOB_BN_MODE_BWD = 17,
+  KNOB_BN_FUSED_ROWS = 18,
+  KNOB_DW_MAIN = 19,
+  KNOB_PAIR_ROWS = 20,
+  KNOB_DW_MAIN_PING = 21,
+  KNOB_EV_EVERY = 22,
+  KNOB_LOSS_SIDE = 23,
+  KNOB_DP_SMALL_AT = 24,
+  KNOB_KEEP_GRADS = 25,
+  KNOB_SIDE_PRIO = 26,
+  KNOB_EVENT_SYSFENCE = 27,
+  KNOB_DP_SHARD = 28,
+  KNOB_SIDE_HOLD = 29,
+  KNOB_DP_BUCKET_MIB = 30,
+  KNOB_EV_ON_KERNEL = 31,
+  KNOB_SPLITK_DW_F32_BLOCKS = 32,
+  KNOB_DW_LATE = 33,
+  KNOB_FORK_ON_KERNEL = 34,
+  KNOB_FORK_PAIR_BELOW = 35,
+  KNOB_COUNT_
+};
+static_assert(KNOB_COUNT_ == MMAD_KNOB_COUNT, "MmadKnob names every slot of the tune table");
+
+int mmad_knob(MmadKnob k);     // the tune table (mmad_tune_set)
 int mmad_group_override();
 
 int mmad_tile_override();

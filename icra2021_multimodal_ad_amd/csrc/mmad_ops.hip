@@ -1095,7 +1095,7 @@ int mmad_bn_act_bwd_apply_ev(int dtype, int act, float slope, int M, int N, int 
   // 128-row slabs per block (knob 13: 1, 2 or 4; any other value = 1; halved
   // until it divides the row slabs): the column partials are merged once per
   // block instead of once per 128-row slab
-  int rb = mmad_knob(13);
+  int rb = mmad_knob(KNOB_BN_APPLY_RB);
   if (rb != 1 && rb != 2 && rb != 4) rb = 1;
   while (rb > 1 && (Mp / SLAB_ROWS) % rb) rb >>= 1;
   dim3 grd(Np / SLAB_COLS, Mp / (SLAB_ROWS * rb));

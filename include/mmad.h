@@ -57,6 +57,11 @@ int mmad_pad_granule(void);
  * through mmad_tune_set (the library reads no environment variables).  GEMM
  * knobs are read per dispatch; the executor's schedule knobs (14-31, 33-35) are
  * copied into a handle by mmad_ae_create, so set them before creating it.
+ * For an executor handle, whether knobs 4 / 9 / 10 / 32 can split a GEMM at
+ * all is fixed at mmad_ae_create as well: the handle's workspace holds the
+ * split-K slabs only if one of them allowed a split then (4 > 1; 4 == 0 and,
+ * bf16: 9 > 1 or 10 > 0, fp32: 32 > 0).  With the slabs the factor follows
+ * the knobs per dispatch; without them no GEMM of the handle ever splits.
  *   0  GEMM tile override (-1 autotuned; 0 = 128x128/512 thr, 1 = 256x128,
  *      2 = 128x256, 3 = 64x64/256 thr, 4 = 64x128, 5 = 128x128/256 thr,
  *      6 = 256x256/512 thr (bf16 forward / MSE / score GEMMs without fused BN
@@ -858,9 +863,11 @@ int mmad_ae_online_score_groups(mmad_ae* h, const float* x, int ld_x, int B, int
                                 float* group_out, uint8_t* group_flags, void* gstate,
                                 int64_t gstate_bytes);
 
-/* Split-K health of the executor workspace `ws` (as mmad_gemm_status): a
- * no-op returning MMAD_OK unless split-K is enabled (tuning knob 4 > 1);
- * otherwise synchronises `stream` and returns MMAD_EHIP if any GEMM combine
+/* Split-K / fused-BN health of the executor workspace `ws` (as
+ * mmad_gemm_status): a no-op returning MMAD_OK for a handle whose schedule,
+ * fixed at mmad_ae_create, holds neither the split-K slabs (tuning knobs 4 /
+ * 9 / 10 / 32, above) nor a fused BN mode (16 / 17), whatever the knobs say
+ * now; otherwise synchronises `stream` and returns MMAD_EHIP if any GEMM combine
  * of the calls since the last check timed out. */
 int mmad_ae_status(mmad_ae* h, void* ws, int64_t ws_bytes, void* stream);
 

@@ -21,14 +21,16 @@ STATE = ("params", "exp_avg", "exp_avg_sq", "running")
 
 def _run(model, d, dtype, rows, knobs, probe_layer=-1, step_knobs=(), steps=3):
     """`steps` fused train steps of a fresh model from one seed under `knobs`
-    (set while the model is built; `step_knobs` also while it steps).  Returns
-    (state tensors on the host, losses, probe layer mask of the last step)."""
+    (set while the model is built; `step_knobs` then and while it steps: a
+    handle takes the split-K slabs only if a split knob is set when it is
+    created).  Returns (state tensors on the host, losses, probe layer mask of
+    the last step)."""
     from icra2021_multimodal_ad_amd.model_builder import get_model
     lib = _native.load()
     knobs, step_knobs = dict(knobs), dict(step_knobs)
     cfg = types.SimpleNamespace(input_size=d, btl_size=16, n_layers=5, gpu_id=0, dtype=dtype, models=model)
     torch.manual_seed(8)
-    with _native.tune(**knobs):
+    with _native.tune(**knobs, **step_knobs):
         m = get_model(cfg)
     nat = m._native
     nat.sync_shadow(force=True)
