@@ -1419,6 +1419,9 @@ int mmad_vib_reparam_bwd(int dtype, int B, int btl, int k, const void* enc_out, 
                          void* d_enc_out, int ld_denc, float* colsum, void* stream) {
   MMAD_NO_X3(dtype, "vib_reparam_bwd");
   MMAD_CHECK_ARG(B >= 1 && btl >= 1 && k >= 1 && ld_denc >= 2 * btl, "vib_reparam_bwd: bad sizes");
+  // the column sums run on 64-column slabs with 16-byte loads
+  MMAD_CHECK_ARG(!colsum || ld_denc % SLAB_COLS == 0,
+                 "vib_reparam_bwd: colsum needs ld_denc to be a multiple of 64, got %d", ld_denc);
   const int Mpe = mmad_roundup(B, MMAD_PAD);
   const int64_t n = (int64_t)Mpe * ld_denc;
   hipStream_t s = (hipStream_t)stream;

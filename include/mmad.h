@@ -447,8 +447,11 @@ int mmad_adam(int64_t n, float* p, const float* g, float* m, float* v, float bet
  * z (dtype, [Mpz][ld_z]) for kk < k.  eps: injected fp32 [k][B][btl]
  * (nullable -> Philox N(0,1) from seed/offset; the draw is stored to eps_out,
  * nullable).  deterministic != 0 -> z = mu (no_grad and not stochastic).
- * kl_partial (nullable): fp32 [Mp/128] partial sums of
- * -0.5*(1 + lv - mu^2 - exp(lv)) (build-defined KL, SURVEY §8 a10').
+ * kl_partial (nullable): fp32 partial sums of
+ * -0.5*(1 + lv - mu^2 - exp(lv)) over the first B rows (build-defined KL,
+ * SURVEY §8 a10'), one per 256 elements of the packed z buffer:
+ * ceil(roundup(k*B, 128) * ld_z / 256) floats, all written.  Only their sum
+ * is defined; which partial holds which rows is not.
  * MMAD_BF16X3: only deterministic != 0 with kl_partial == NULL (z = mu, a
  * copy of both planes; B rounded up to the granule locates enc_out's lo
  * plane); MMAD_EUNSUPPORTED otherwise. */
@@ -458,7 +461,9 @@ int mmad_vib_reparam_fwd(int dtype, int B, int btl, int k, const void* enc_out, 
 
 /* Backward of the reparameterisation + beta*KL: dz [k*B rows][ld_dz] (dtype)
  * -> d_enc_out (dtype [Mp][ld_denc], mu|logvar columns); colsum (nullable)
- * receives column-sum partials [Mp/128][ld_denc] for the encoder's last bias. */
+ * receives column-sum partials [Mp/128][ld_denc] for the encoder's last bias;
+ * with colsum given, ld_denc must be a multiple of 64 (the column slab of the
+ * reduction; MMAD_EINVAL otherwise, nothing launched). */
 int mmad_vib_reparam_bwd(int dtype, int B, int btl, int k, const void* enc_out, int ld_enc,
                          const float* eps, const void* dz, int ld_dz, float beta_kl,
                          void* d_enc_out, int ld_denc, float* colsum, void* stream);

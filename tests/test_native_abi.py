@@ -62,6 +62,21 @@ def test_abi_constants_and_errors(lib):
     assert lib.mmad_gemm_tile_for(7, 1, 0, 256, 256, 1, 0, 1, 0) == 6
 
 
+def test_vib_bwd_colsum_needs_whole_column_slabs(lib):
+    """mmad_vib_reparam_bwd reduces d_enc_out on 64-column slabs: with colsum
+    given, an ld_denc that is no multiple of 64 is refused on the host before
+    any launch (the pointers are never read)."""
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.c_void_p(ctypes.addressof(buf))
+    for ld_denc in (32, 100, 200):
+        rc = lib.mmad_vib_reparam_bwd(0, 8, 16, 1, p, 32, p, p, 16, 0.0, p, ld_denc, p, None)
+        assert rc == -1, ld_denc
+        assert b"multiple of 64" in lib.mmad_last_error_string()
+    # the size check that was there before still comes first
+    assert lib.mmad_vib_reparam_bwd(0, 8, 16, 1, p, 32, p, p, 16, 0.0, p, 16, p, None) == -1
+    assert b"bad sizes" in lib.mmad_last_error_string()
+
+
 def test_tune_table_names_and_defaults(lib):
     """_native.KNOB names exactly the knobs include/mmad.h documents (a slot
     past the table is refused), and the table starts at the documented
