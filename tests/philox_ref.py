@@ -1,4 +1,4 @@
-"""Numpy restatement of the VIB noise draw (philox_normal, csrc/mmad_ops.hip):
+"""Numpy restatement of the VIB noise draw (philox_normal, csrc/mmad_ops_vib.hip):
 Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3",
 SC'11) keyed by the 64-bit seed, counter = (element index, offset), the first
 two output words turned into one N(0,1) value by Box-Muller in float64.

@@ -1,4 +1,4 @@
-"""The BN-backward apply kernel (bn_bwd_apply_k, csrc/mmad_ops.hip) on its own,
+"""The BN-backward apply kernel (bn_bwd_apply_k, csrc/mmad_ops_bn_bwd.hip) on its own,
 against a float64 torch restatement of the formula it evaluates -- the
 backward of layers/fc_layer.py:39-45's BatchNorm1d(act(Linear)) as autograd
 forms it:

@@ -1,4 +1,4 @@
-"""The layer operators between the GEMMs (csrc/mmad_ops.hip), fp32 and bf16,
+"""The layer operators between the GEMMs (csrc/mmad_ops_*.hip), fp32 and bf16,
 through the public C-ABI at the edges where the 64-column x 128-row slab
 kernels index differently: a batch that ends inside a 32-row statistics
 chunk, inside / at / one past a 128-row slab, widths at 63 / 64 / 65 of a

@@ -1,5 +1,6 @@
 """The VIB waist as operators: mmad_vib_reparam_fwd / mmad_vib_reparam_bwd
-(vib_fwd_k, vib_bwd_k, philox_normal and the colsum pass, csrc/mmad_ops.hip)
+(vib_fwd_k, vib_bwd_k, philox_normal, csrc/mmad_ops_vib.hip; the colsum pass,
+csrc/mmad_ops_reduce.hip)
 through the public C-ABI, against float64 of the values the kernels read.
 
 * the generated noise (eps = NULL) against the numpy Philox4x32-10 +

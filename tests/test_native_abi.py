@@ -77,6 +77,35 @@ def test_vib_bwd_colsum_needs_whole_column_slabs(lib):
     assert b"bad sizes" in lib.mmad_last_error_string()
 
 
+def test_operator_entries_refuse_unknown_dtype(lib):
+    """Every layer-operator entry picks its kernel through one element-type
+    dispatch: a dtype that is none of MMAD_F32 / MMAD_BF16 / MMAD_BF16X3 is
+    refused on the host with MMAD_EINVAL "bad dtype" (it used to run the fp32
+    kernel), and the entries without a plane form refuse MMAD_BF16X3 with
+    MMAD_EUNSUPPORTED.  Sizes are valid (128 everywhere; the VIB entries take
+    btl = 64 so that ld_enc = 128 holds mu | logvar), so the dtype is the only
+    thing to refuse; nothing is launched and the pointers are never read."""
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.c_void_p(ctypes.addressof(buf))
+    err = lib.mmad_last_error_string
+    n = 128
+    entries = {
+        "mmad_bn_train_apply": lambda dt: (dt, n, n, n, n, p, p, p, p, p, p, 0.1, 1e-5, p, p, p, None),
+        "mmad_bn_act_bwd": lambda dt: (dt, 1, 0.2, n, n, n, n, p, p, p, p, p, p, p, p, p, p, None),
+        "mmad_act_bwd": lambda dt: (dt, 1, 0.2, n, n, n, p, p, p, p, None),
+        "mmad_vib_reparam_bwd": lambda dt: (dt, n, 64, 1, p, n, p, p, n, 0.0, p, n, p, None),
+        "mmad_vib_reparam_fwd": lambda dt: (dt, n, 64, 1, p, n, None, None, 0, 0, 1, p, n, None, None),
+        "mmad_pack_input": lambda dt: (dt, n, n, n, n, p, n, p, None),
+        "mmad_unpack_output": lambda dt: (dt, n, n, n, p, p, n, None),
+    }
+    for name, args in entries.items():
+        assert getattr(lib, name)(*args(7)) == -1, name
+        assert b"bad dtype 7" in err(), (name, err())
+    for name in list(entries)[:4]:                   # no split-bf16 form
+        assert getattr(lib, name)(*entries[name](2)) == -2, name
+        assert b"MMAD_BF16X3 covers the eval / score path only" in err(), (name, err())
+
+
 def test_tune_table_names_and_defaults(lib):
     """_native.KNOB names exactly the knobs include/mmad.h documents (a slot
     past the table is refused), and the table starts at the documented
