@@ -25,6 +25,32 @@ _F = ctypes.c_float
 _I64 = ctypes.c_int64
 _U64 = ctypes.c_uint64
 
+SRC_U8, SRC_F32 = 1, 4   # MMAD_SRC_*: the element types mmad_hsr_fuse_raw takes
+
+
+class TickArgs(ctypes.Structure):
+    """mmad_tick_args (include/mmad.h), field for field."""
+    _fields_ = [
+        ("pcm", _P), ("pcm_type", _I), ("L", _I64),
+        ("r", _P), ("r_type", _I),
+        ("d", _P), ("d_type", _I),
+        ("t", _P),
+        ("range_in", _F * 6), ("norm_rcp", _I),
+        ("sr", _I), ("n_fft", _I), ("n_mels", _I), ("n_mfcc", _I),
+        ("plan", _P), ("plan_bytes", _I64),
+        ("mfcc_out", _P), ("mfcc_out_bytes", _I64),
+        ("mfcc_norm", _P), ("mfcc_norm_bytes", _I64),
+        ("mfcc_ws", _P), ("mfcc_ws_bytes", _I64),
+        ("hsr_weights", _P), ("hsr_weight_count", _I),
+        ("x", _P), ("ld_x", _I), ("B", _I), ("rows", _I), ("sap_start", _I), ("sap_end", _I),
+        ("thresholds", _P), ("out", _P), ("flags", _P),
+        ("state", _P), ("state_bytes", _I64),
+        ("bounds", ctypes.POINTER(_I)), ("G", _I),
+        ("group_thresholds", _P), ("group_out", _P), ("group_flags", _P),
+        ("gstate", _P), ("gstate_bytes", _I64),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/mmad.h one-to-one
 SIGNATURES = {
     "mmad_last_error_string": (ctypes.c_char_p, []),
@@ -162,6 +188,8 @@ SIGNATURES = {
     "mmad_mfcc_plan_init": (_I, [_P, _I64, _I, _I, _I, _I, _P]),
     "mmad_mfcc_ws_bytes": (_I64, [_I64, _I]),
     "mmad_mfcc": (_I, [_P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _I64, _F, _F, _P, _P, _I64, _P]),
+    "mmad_hsr_fuse_raw": (_I, [_I, _P, _I, _P, _I, _P, _P, _F, _F, _F, _F, _F, _F, _P, _I, _P, _I, _P]),
+    "mmad_ae_online_tick": (_I, [_P, ctypes.POINTER(TickArgs), _I, _P]),
 }
 
 

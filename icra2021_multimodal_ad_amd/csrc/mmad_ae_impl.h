@@ -80,6 +80,24 @@ struct ScoreKey {
 // the entry point's row capacity (16 / 64: other kernels, other layouts).  A
 // grouped pass (mmad_ae_online_score_groups) adds G > 0, the bounds' values
 // (zero beyond G) and its buffers; an ungrouped one leaves them all zero
+// A sensor tick (mmad_ae_online_tick) adds what its front launches read and
+// write: the raw queues and their types, the MFCC parameters and buffers, the
+// packed HSR weights and the ranges; a pass without the front leaves them zero
+struct TickKey {
+  const void *pcm = nullptr, *r = nullptr, *d = nullptr, *t = nullptr;
+  int pcm_type = 0, r_type = 0, d_type = 0;
+  int64_t L = 0;
+  int sr = 0, n_fft = 0, n_mels = 0, n_mfcc = 0;
+  const void *plan = nullptr, *mfcc_ws = nullptr, *mfcc_out = nullptr, *mfcc_norm = nullptr, *hsr_w = nullptr;
+  float range_in[6] = {};
+  int norm_rcp = 0;
+  bool operator==(const TickKey& o) const {
+    return norm_rcp == o.norm_rcp && pcm == o.pcm && r == o.r && d == o.d && t == o.t && pcm_type == o.pcm_type && r_type == o.r_type &&
+           d_type == o.d_type && L == o.L && sr == o.sr && n_fft == o.n_fft && n_mels == o.n_mels &&
+           n_mfcc == o.n_mfcc && plan == o.plan && mfcc_ws == o.mfcc_ws && mfcc_out == o.mfcc_out &&
+           mfcc_norm == o.mfcc_norm && hsr_w == o.hsr_w && std::equal(range_in, range_in + 6, o.range_in);
+  }
+};
 struct OnlineKey {
   const float* x; int ld_x, B, sap_start, sap_end; const float* thr; float* out; uint8_t* flags;
   void* state; const void* wts; const void* nap_vt;
@@ -87,12 +105,13 @@ struct OnlineKey {
   int G = 0;
   int bounds[MMAD_MAX_GROUPS + 1] = {};
   const float* gthr = nullptr; float* gout = nullptr; uint8_t* gflags = nullptr; void* gstate = nullptr;
+  TickKey tick;
   bool operator==(const OnlineKey& o) const {
     return x == o.x && ld_x == o.ld_x && B == o.B && sap_start == o.sap_start && sap_end == o.sap_end &&
            thr == o.thr && out == o.out && flags == o.flags && state == o.state && wts == o.wts &&
            nap_vt == o.nap_vt && rows == o.rows && G == o.G &&
            std::equal(bounds, bounds + MMAD_MAX_GROUPS + 1, o.bounds) && gthr == o.gthr &&
-           gout == o.gout && gflags == o.gflags && gstate == o.gstate;
+           gout == o.gout && gflags == o.gflags && gstate == o.gstate && tick == o.tick;
   }
 };
 // ... of a captured fused train step (mmad_ae_train_step_graph)

@@ -167,12 +167,38 @@ int64_t mmad_ae_online_groups_bytes(const mmad_ae* h, int rows) {
   return ((int64_t)rows * h->L[0].Kp * 4 + 255) / 256 * 256;
 }
 
-// the entry points; rows = 16 (mmad_ae_online_score) or 64 (_score64); gr:
-// the grouped form's arguments, checked here (d0 filled in)
-static int online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
+// the grouped forms' own refusals (rows, G, bounds); fills gr but for d0
+static int groups_check(int rows, const int* bounds, int G, const float* group_thresholds, float* group_out,
+                        uint8_t* group_flags, OnlineGroups& gr) {
+  MMAD_CHECK_ARG(rows == 16 || rows == 64, "ae_online_score_groups: rows=%d (16 or 64)", rows);
+  MMAD_CHECK_ARG(G >= 1 && G <= MMAD_MAX_GROUPS, "ae_online_score_groups: G=%d outside 1..%d", G,
+                 MMAD_MAX_GROUPS);
+  MMAD_CHECK_ARG(bounds && bounds[0] >= 0, "ae_online_score_groups: bounds null or bounds[0] negative");
+  gr = OnlineGroups{};
+  gr.G = G;
+  for (int g = 0; g <= G; ++g) gr.bounds[g] = bounds[g];
+  for (int g = 0; g < G; ++g)
+    MMAD_CHECK_ARG(bounds[g] < bounds[g + 1], "ae_online_score_groups: bounds not strictly ascending "
+                   "(bounds[%d]=%d, bounds[%d]=%d)", g, bounds[g], g + 1, bounds[g + 1]);
+  gr.thr = group_thresholds; gr.out = group_out; gr.flags = group_flags;
+  return MMAD_OK;
+}
+
+// one call of an entry point, checked: the carved state, the clamped SAP range
+// and the pass's graph signature
+struct OnlineCall {
+  OnlineWS o;
+  int s0, s1;
+  OnlineKey key;
+};
+
+// every refusal of the entry points; rows = 16 (mmad_ae_online_score) or 64
+// (_score64); gr: the grouped form's arguments, checked here (d0 filled in).
+// Nothing is launched.
+static int online_check(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
                         const float* thresholds, float* out, uint8_t* flags, void* state,
-                        int64_t state_bytes, int use_graph, void* stream, int rows,
-                        OnlineGroups* gr = nullptr, void* gstate = nullptr, int64_t gstate_bytes = 0) {
+                        int64_t state_bytes, int rows, OnlineGroups* gr, void* gstate,
+                        int64_t gstate_bytes, OnlineCall& c) {
   MMAD_CHECK_ARG(h, "ae_online_score: null handle");
   if (gr) {
     MMAD_CHECK_ARG(gr->bounds[gr->G] <= h->L[0].K, "ae_online_score_groups: bounds[G]=%d exceeds the "
@@ -207,25 +233,29 @@ static int online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_sta
   if (s0 > nd - 1) s0 = nd - 1;
   if (s1 - s0 < 1) s1 = s0 + 1;
   if (s1 > nd) s1 = nd;
-  hipStream_t st = (hipStream_t)stream;
-  OnlineWS o;
-  online_carve(h, (char*)state, o, rows);
-  const void* tag = (const char*)state + (rows == 16 ? 0 : 1);   // mmad_ae::online_ready
+  c.s0 = s0; c.s1 = s1;
+  online_carve(h, (char*)state, c.o, rows);
+  const void* nap_vt = h->nap.on ? (const void*)h->nap.vt : nullptr;
+  c.key = OnlineKey{x, ld_x, B, s0, s1, thresholds, out, flags, state, weights(h, h->L[0]), nap_vt, rows};
+  if (gr) {
+    c.key.G = gr->G;
+    for (int g = 0; g <= gr->G; ++g) c.key.bounds[g] = gr->bounds[g];
+    c.key.gthr = gr->thr; c.key.gout = gr->out; c.key.gflags = gr->flags; c.key.gstate = gstate;
+  }
+  return MMAD_OK;
+}
+
+// a checked call's launches: pass(stream) eagerly, or (use_graph) the replay
+// of its capture under key, made on the first call
+template <class Pass>
+static int online_run(mmad_ae* h, const OnlineWS& o, const OnlineKey& key, int use_graph, hipStream_t st,
+                      Pass pass) {
+  const void* tag = (const char*)key.state + (key.rows == 16 ? 0 : 1);   // mmad_ae::online_ready
   if (h->nap.on && h->online_ready != tag) {
-    MMAD_HIP_CHECK(hipMemsetAsync(o.nap_x, 0, (size_t)rows * h->nap.Kp * 4, st));
+    MMAD_HIP_CHECK(hipMemsetAsync(o.nap_x, 0, (size_t)key.rows * h->nap.Kp * 4, st));
     h->online_ready = tag;
   }
-  auto pass = [&](hipStream_t s) {
-    return online_pass(h, x, ld_x, B, s0, s1, thresholds, out, flags, o, rows, s, gr);
-  };
   if (!use_graph) return pass(st);
-  const void* nap_vt = h->nap.on ? (const void*)h->nap.vt : nullptr;
-  OnlineKey key{x, ld_x, B, s0, s1, thresholds, out, flags, state, weights(h, h->L[0]), nap_vt, rows};
-  if (gr) {
-    key.G = gr->G;
-    for (int g = 0; g <= gr->G; ++g) key.bounds[g] = gr->bounds[g];
-    key.gthr = gr->thr; key.gout = gr->out; key.gflags = gr->flags; key.gstate = gstate;
-  }
   if (hipGraphExec_t hit = h->ographs.find(key)) {
     MMAD_HIP_CHECK(hipGraphLaunch(hit, st));
     return MMAD_OK;
@@ -235,6 +265,18 @@ static int online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_sta
   RET_IF(capture_error(capture_graph(h, pass, &exec)));
   h->ographs.insert(key, exec);   // bounded cache: drops the oldest pass
   return MMAD_OK;
+}
+
+static int online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
+                        const float* thresholds, float* out, uint8_t* flags, void* state,
+                        int64_t state_bytes, int use_graph, void* stream, int rows,
+                        OnlineGroups* gr = nullptr, void* gstate = nullptr, int64_t gstate_bytes = 0) {
+  OnlineCall c;
+  RET_IF(online_check(h, x, ld_x, B, sap_start, sap_end, thresholds, out, flags, state, state_bytes, rows, gr,
+                      gstate, gstate_bytes, c));
+  return online_run(h, c.o, c.key, use_graph, (hipStream_t)stream, [&](hipStream_t s) {
+    return online_pass(h, x, ld_x, B, c.s0, c.s1, thresholds, out, flags, c.o, rows, s, gr);
+  });
 }
 
 int mmad_ae_online_score(mmad_ae* h, const float* x, int ld_x, int B, int sap_start, int sap_end,
@@ -256,17 +298,54 @@ int mmad_ae_online_score_groups(mmad_ae* h, const float* x, int ld_x, int B, int
                                 int64_t state_bytes, int use_graph, void* stream, int rows,
                                 const int* bounds, int G, const float* group_thresholds, float* group_out,
                                 uint8_t* group_flags, void* gstate, int64_t gstate_bytes) {
-  MMAD_CHECK_ARG(rows == 16 || rows == 64, "ae_online_score_groups: rows=%d (16 or 64)", rows);
-  MMAD_CHECK_ARG(G >= 1 && G <= MMAD_MAX_GROUPS, "ae_online_score_groups: G=%d outside 1..%d", G,
-                 MMAD_MAX_GROUPS);
-  MMAD_CHECK_ARG(bounds && bounds[0] >= 0, "ae_online_score_groups: bounds null or bounds[0] negative");
   OnlineGroups gr{};
-  gr.G = G;
-  for (int g = 0; g <= G; ++g) gr.bounds[g] = bounds[g];
-  for (int g = 0; g < G; ++g)
-    MMAD_CHECK_ARG(bounds[g] < bounds[g + 1], "ae_online_score_groups: bounds not strictly ascending "
-                   "(bounds[%d]=%d, bounds[%d]=%d)", g, bounds[g], g + 1, bounds[g + 1]);
-  gr.thr = group_thresholds; gr.out = group_out; gr.flags = group_flags;
+  RET_IF(groups_check(rows, bounds, G, group_thresholds, group_out, group_flags, gr));
   return online_score(h, x, ld_x, B, sap_start, sap_end, thresholds, out, flags, state, state_bytes,
                       use_graph, stream, rows, &gr, gstate, gstate_bytes);
+}
+
+// ---- the sensor tick: mmad_mfcc -> mmad_hsr_fuse_raw -> the pass above, one
+// launch list (one graph).  Every component's refusals run first; the launches
+// are the components' own entry points on the one stream.
+int mmad_ae_online_tick(mmad_ae* h, const mmad_tick_args* a, int use_graph, void* stream) {
+  MMAD_CHECK_ARG(h && a, "ae_online_tick: null handle or arguments");
+  MMAD_CHECK_ARG(a->rows == 16 || a->rows == 64, "ae_online_tick: rows=%d (16 or 64)", a->rows);
+  OnlineGroups gr{};
+  const bool grouped = a->bounds != nullptr;
+  if (grouped)
+    RET_IF(groups_check(a->rows, a->bounds, a->G, a->group_thresholds, a->group_out, a->group_flags, gr));
+  OnlineCall c;
+  RET_IF(online_check(h, a->x, a->ld_x, a->B, a->sap_start, a->sap_end, a->thresholds, a->out, a->flags,
+                      a->state, a->state_bytes, a->rows, grouped ? &gr : nullptr, a->gstate, a->gstate_bytes, c));
+  MMAD_CHECK_ARG(h->L[0].K == 1728, "ae_online_tick: the model's input width %d is not the fused row's 1728",
+                 h->L[0].K);
+  RET_IF(mmad_mfcc_check(a->pcm, a->pcm_type, a->L, a->sr, a->n_fft, a->n_mels, a->n_mfcc, a->plan, a->plan_bytes,
+                         a->mfcc_out, a->B, a->mfcc_norm, a->mfcc_ws, a->mfcc_ws_bytes));
+  const int64_t F = mmad_mfcc_frames(a->L, a->n_fft);
+  MMAD_CHECK_ARG(a->mfcc_norm && a->mfcc_out_bytes >= F * a->n_mfcc * 4 &&
+                 a->mfcc_norm_bytes >= (int64_t)a->B * a->n_mfcc * 4,
+                 "ae_online_tick: mfcc_out / mfcc_norm null or too small (%lld / %lld bytes for %lld / %d frames)",
+                 (long long)a->mfcc_out_bytes, (long long)a->mfcc_norm_bytes, (long long)F, a->B);
+  MMAD_CHECK_ARG(a->n_mfcc == 13, "ae_online_tick: n_mfcc=%d, the fusion producer reads 13 coefficients a frame",
+                 a->n_mfcc);
+  MMAD_CHECK_ARG(a->hsr_weight_count >= mmad_hsr_weight_count(), "ae_online_tick: %d packed HSR weights, needs %d",
+                 a->hsr_weight_count, mmad_hsr_weight_count());
+  RET_IF(mmad_hsr_fuse_raw_check(a->B, a->r, a->r_type, a->d, a->d_type, a->t, a->mfcc_norm, a->range_in,
+                                 a->hsr_weights, 0, a->x, a->ld_x));
+  TickKey& k = c.key.tick;
+  k.pcm = a->pcm; k.r = a->r; k.d = a->d; k.t = a->t;
+  k.pcm_type = a->pcm_type; k.r_type = a->r_type; k.d_type = a->d_type;
+  k.L = a->L; k.sr = a->sr; k.n_fft = a->n_fft; k.n_mels = a->n_mels; k.n_mfcc = a->n_mfcc;
+  k.plan = a->plan; k.mfcc_ws = a->mfcc_ws; k.mfcc_out = a->mfcc_out; k.mfcc_norm = a->mfcc_norm;
+  k.hsr_w = a->hsr_weights;
+  for (int i = 0; i < 6; ++i) k.range_in[i] = a->range_in[i];
+  k.norm_rcp = a->norm_rcp != 0;
+  return online_run(h, c.o, c.key, use_graph, (hipStream_t)stream, [&](hipStream_t s) {
+    RET_IF(mmad_mfcc(a->pcm, a->pcm_type, a->L, a->sr, a->n_fft, a->n_mels, a->n_mfcc, a->plan, a->plan_bytes,
+                     a->mfcc_out, a->B, -1.f, 1.f, a->mfcc_norm, a->mfcc_ws, a->mfcc_ws_bytes, s));
+    RET_IF(mmad_hsr_fuse_raw_launch(a->B, a->r, a->r_type, a->d, a->d_type, a->t, a->mfcc_norm, a->range_in,
+                                    a->norm_rcp, a->hsr_weights, 0, a->x, a->ld_x, s));
+    return online_pass(h, a->x, a->ld_x, a->B, c.s0, c.s1, a->thresholds, a->out, a->flags, c.o, a->rows, s,
+                       grouped ? &gr : nullptr);
+  });
 }

@@ -9,8 +9,16 @@
 // :217-220).  fp32 throughout (the reference's dtype); the weights are
 // wave-uniform reads (scalar cache), activations live in LDS, and each output
 // channel plane is one coalesced 64- or 256-float store into the window's row.
+// mmad_hsr_fuse_raw is the same body reading the sensor queues' own uint8 /
+// fp32 elements, norm_vec folded into the loads (the loaders below).
 #include "mmad_common.h"
 #include "mmad_ops.h"
+
+#define RET_IF_HSR(x)                \
+  do {                               \
+    int r_ = (x);                    \
+    if (r_ != MMAD_OK) return r_;    \
+  } while (0)
 
 namespace {
 // packed weight layout (mmad_hsr_weight_count floats), torch shapes [co][ci][k..]
@@ -34,11 +42,49 @@ constexpr int NWEIGHTS = B2L + 16;
 
 __device__ __forceinline__ float relu(float v) { return v > 0.f ? v : 0.f; }
 
+// How the kernels read a window's image and force values.  Plain: fp32 as
+// stored (mmad_hsr_fuse).  Raw<T>: the sensor queue's own element type T
+// (uint8_t or float) through norm_vec to [-1, 1] (mmad_hsr_fuse_raw): fp32,
+// every operation rounded on its own -- ((2 (v - lo)) / (hi - lo)) + (-1), a
+// true division, nothing contracted: IEEE fp32, the bits of torch's elementwise
+// chain on the host.  inv != 0 (mmad_ae_online_tick's norm_rcp only): the
+// quotient is the product with inv = fl(1 / (hi - lo)) instead, rounded once --
+// what torch's DEVICE kernels compute for tensor / Python scalar.
+// pair(i): elements i, i + 1 with i even (one row of a thread's 2x2 patch).
+struct Plain {
+  const float* __restrict__ p;
+  __device__ __forceinline__ Plain at(size_t off) const { return Plain{p + off}; }
+  __device__ __forceinline__ float one(int i) const { return p[i]; }
+  __device__ __forceinline__ void pair(int i, float& a, float& b) const { a = p[i]; b = p[i + 1]; }
+};
+template <typename T> struct Raw {
+  const T* __restrict__ p;
+  float lo, span, inv;   // span = hi - lo; inv: 0, or fl(1 / span)
+  __device__ __forceinline__ Raw at(size_t off) const { return Raw{p + off, lo, span, inv}; }
+  __device__ __forceinline__ float norm(float v) const {
+#pragma clang fp contract(off)
+    const float n2 = __fmul_rn(2.f, __fsub_rn(v, lo));
+    const float q = inv != 0.f ? __fmul_rn(n2, inv) : __fdiv_rn(n2, span);   // wave-uniform choice
+    return __fadd_rn(q, -1.f);
+  }
+  __device__ __forceinline__ float one(int i) const { return norm((float)p[i]); }
+  __device__ __forceinline__ void pair(int i, float& a, float& b) const {
+    if constexpr (sizeof(T) == 1) {
+      // one 2-byte load (the host checks the alignment): lanes x = 0..15 of a
+      // patch row read 32 contiguous bytes
+      const uchar2 v = *(const uchar2*)(p + i);
+      a = norm((float)v.x); b = norm((float)v.y);
+    } else {
+      a = norm((float)p[i]); b = norm((float)p[i + 1]);
+    }
+  }
+};
+
 // One image stack: C0 input planes of 32x32 -> C channels: 2x2/s2 (16x16),
 // 3x3/p1 (16x16), 2x2/s2 (8x8).  Thread tid owns position (y, x) of the
 // 16x16 planes, then 64 output positions x (C*64/256) channels of the last conv.
-template <int C0, int C>
-__device__ __forceinline__ void image_stack(const float* __restrict__ img, const float* __restrict__ w,
+template <int C0, int C, typename Ld>
+__device__ __forceinline__ void image_stack(const Ld img, const float* __restrict__ w,
                                             int w1, int b1, int w2, int b2, int w3, int b3,
                                             float* sA, float* sB, float* __restrict__ orow, int tid) {
   const int y = tid >> 4, x = tid & 15;
@@ -48,9 +94,7 @@ __device__ __forceinline__ void image_stack(const float* __restrict__ img, const
     for (int ic = 0; ic < C0; ++ic)
 #pragma unroll
       for (int ky = 0; ky < 2; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 2; ++kx)
-          in[ic * 4 + ky * 2 + kx] = img[ic * 1024 + (2 * y + ky) * 32 + 2 * x + kx];
+        img.pair(ic * 1024 + (2 * y + ky) * 32 + 2 * x, in[ic * 4 + ky * 2], in[ic * 4 + ky * 2 + 1]);
 #pragma unroll
     for (int oc = 0; oc < C; ++oc) {
       float acc = w[b1 + oc];
@@ -108,20 +152,22 @@ __device__ __forceinline__ void image_stack(const float* __restrict__ img, const
 }
 
 // one workgroup per window; offsets < 0 = modality absent
-__global__ __launch_bounds__(256) void hsr_fuse_k(const float* __restrict__ r, const float* __restrict__ d,
-                                                  const float* __restrict__ t, const float* __restrict__ m,
-                                                  const float* __restrict__ w, float* __restrict__ out,
-                                                  int ld_out, int off_r, int off_d, int off_t, int off_m) {
+struct HsrOffsets { int r, d, t, m, width; };
+
+template <typename LR, typename LD, typename LT>
+__device__ __forceinline__ void hsr_fuse_body(const LR r, const LD d, const LT t, const float* __restrict__ m,
+                                              const float* __restrict__ w, float* __restrict__ out,
+                                              int ld_out, HsrOffsets off) {
   __shared__ float sA[16 * 256], sB[16 * 256], sM[16];
   const int tid = threadIdx.x;
   const size_t win = blockIdx.x;
   float* orow = out + win * (size_t)ld_out;
-  if (off_r >= 0)
-    image_stack<3, 16>(r + win * 3072, w, W1R, B1R, W2R, B2R, W3R, B3R, sA, sB, orow + off_r, tid);
-  if (off_d >= 0)
-    image_stack<1, 8>(d + win * 1024, w, W1D, B1D, W2D, B2D, W3D, B3D, sA, sB, orow + off_d, tid);
-  if (off_t >= 0 && tid < 64) orow[off_t + tid] = t[win];   // t[i].repeat(1,1,8,8)
-  if (off_m >= 0) {
+  if (off.r >= 0)
+    image_stack<3, 16>(r.at(win * 3072), w, W1R, B1R, W2R, B2R, W3R, B3R, sA, sB, orow + off.r, tid);
+  if (off.d >= 0)
+    image_stack<1, 8>(d.at(win * 1024), w, W1D, B1D, W2D, B2D, W3D, B3D, sA, sB, orow + off.d, tid);
+  if (off.t >= 0 && tid < 64) orow[off.t + tid] = t.at(win).one(0);   // t[i].repeat(1,1,8,8)
+  if (off.m >= 0) {
     // conv1l over 13 MFCCs: 8 channels x 2 positions (input index 9*pos + k - 9)
     const float* mw = m + win * 13;
     if (tid < 16) {
@@ -145,9 +191,50 @@ __global__ __launch_bounds__(256) void hsr_fuse_k(const float* __restrict__ r, c
       for (int ic = 0; ic < 8; ++ic)
 #pragma unroll
         for (int k = 0; k < 2; ++k) acc = fmaf(sM[ic * 2 + k], w[W2L + (oc * 8 + ic) * 2 + k], acc);
-      orow[off_m + tid] = relu(acc);
+      orow[off.m + tid] = relu(acc);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void hsr_fuse_k(const float* __restrict__ r, const float* __restrict__ d,
+                                                  const float* __restrict__ t, const float* __restrict__ m,
+                                                  const float* __restrict__ w, float* __restrict__ out,
+                                                  int ld_out, HsrOffsets off) {
+  hsr_fuse_body(Plain{r}, Plain{d}, Plain{t}, m, w, out, ld_out, off);
+}
+
+// the sensor queues as they are: TR / TD = the image queues' element types,
+// lo / span / inv per stream (r, d, t); m is mmad_mfcc's norm_out, already in [-1, 1]
+struct HsrRanges { float lo[3], span[3], inv[3]; };
+template <typename TR, typename TD>
+__global__ __launch_bounds__(256) void hsr_fuse_raw_k(const TR* __restrict__ r, const TD* __restrict__ d,
+                                                      const float* __restrict__ t, const float* __restrict__ m,
+                                                      HsrRanges g, const float* __restrict__ w,
+                                                      float* __restrict__ out, int ld_out, HsrOffsets off) {
+  hsr_fuse_body(Raw<TR>{r, g.lo[0], g.span[0], g.inv[0]}, Raw<TD>{d, g.lo[1], g.span[1], g.inv[1]},
+                Raw<float>{t, g.lo[2], g.span[2], g.inv[2]}, m, w, out, ld_out, off);
+}
+
+// which blocks a call writes: the fused row, or (unimodal) the block of the
+// last non-null modality of (r, d, t, m), as the reference keeps (:190-221)
+int hsr_select(const char* who, int n, const void* r, const void* d, const void* t, const void* m,
+               const void* weights, int unimodal, const void* out, int ld_out, HsrOffsets& off) {
+  MMAD_CHECK_ARG(n >= 0, "%s: n must be >= 0 (n=%d)", who, n);
+  MMAD_CHECK_ARG(weights && out, "%s: null weights / out", who);
+  off = HsrOffsets{-1, -1, -1, -1, 0};
+  if (unimodal) {
+    // the product computes only the modality the reference keeps
+    if (m) { off.m = 0; off.width = 128; }
+    else if (t) { off.t = 0; off.width = 64; }
+    else if (d) { off.d = 0; off.width = 512; }
+    else if (r) { off.r = 0; off.width = 1024; }
+    else { mmad_set_error("%s: unimodal needs one modality", who); return MMAD_EINVAL; }
+  } else {
+    MMAD_CHECK_ARG(r && d && t && m, "%s: the fused row needs r, d, t and m (data_loaders.py:224)", who);
+    off = HsrOffsets{0, 1024, 1536, 1600, 1728};
+  }
+  MMAD_CHECK_ARG(ld_out >= off.width, "%s: ld_out %d < row width %d", who, ld_out, off.width);
+  return MMAD_OK;
 }
 }  // namespace
 
@@ -155,24 +242,74 @@ int mmad_hsr_weight_count(void) { return NWEIGHTS; }
 
 int mmad_hsr_fuse(int n, const float* r, const float* d, const float* t, const float* m,
                   const float* weights, int unimodal, float* out, int ld_out, void* stream) {
-  MMAD_CHECK_ARG(n >= 0, "hsr_fuse: n must be >= 0 (n=%d)", n);
-  MMAD_CHECK_ARG(weights && out, "hsr_fuse: null weights / out");
-  int off_r = -1, off_d = -1, off_t = -1, off_m = -1, width;
-  if (unimodal) {
-    // the reference keeps the last modality it computed (:190-221); the
-    // product computes only that one
-    if (m) { off_m = 0; width = 128; }
-    else if (t) { off_t = 0; width = 64; }
-    else if (d) { off_d = 0; width = 512; }
-    else if (r) { off_r = 0; width = 1024; }
-    else { mmad_set_error("hsr_fuse: unimodal needs one modality"); return MMAD_EINVAL; }
-  } else {
-    MMAD_CHECK_ARG(r && d && t && m, "hsr_fuse: the fused row needs r, d, t and m (data_loaders.py:224)");
-    off_r = 0; off_d = 1024; off_t = 1536; off_m = 1600; width = 1728;
-  }
-  MMAD_CHECK_ARG(ld_out >= width, "hsr_fuse: ld_out %d < row width %d", ld_out, width);
+  HsrOffsets off;
+  RET_IF_HSR(hsr_select("hsr_fuse", n, r, d, t, m, weights, unimodal, out, ld_out, off));
   if (n == 0) return MMAD_OK;
-  hsr_fuse_k<<<n, 256, 0, (hipStream_t)stream>>>(r, d, t, m, weights, out, ld_out, off_r, off_d, off_t, off_m);
+  hsr_fuse_k<<<n, 256, 0, (hipStream_t)stream>>>(r, d, t, m, weights, out, ld_out, off);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
+// every refusal of mmad_hsr_fuse_raw (mmad_ae_online_tick checks ahead of its
+// first launch); fills the kernel's offsets and ranges
+static int hsr_raw_check(int n, const void* r, int r_type, const void* d, int d_type, const float* t,
+                         const float* m, const float* range_in, const float* weights, int unimodal,
+                         const float* out, int ld_out, HsrOffsets& off, HsrRanges& g) {
+  const char* who = "hsr_fuse_raw";
+  RET_IF_HSR(hsr_select(who, n, r, d, t, m, weights, unimodal, out, ld_out, off));
+  const struct { const char* name; bool used; const void* p; int type; } s[3] = {
+      {"r", off.r >= 0, r, r_type}, {"d", off.d >= 0, d, d_type}, {"t", off.t >= 0, t, MMAD_SRC_F32}};
+  g = HsrRanges{};
+  for (int i = 0; i < 3; ++i) {
+    if (!s[i].used) continue;
+    MMAD_CHECK_ARG(s[i].type == MMAD_SRC_U8 || s[i].type == MMAD_SRC_F32,
+                   "%s: %s of element type %d (MMAD_SRC_U8 or MMAD_SRC_F32)", who, s[i].name, s[i].type);
+    MMAD_CHECK_ARG(((uintptr_t)s[i].p) % (s[i].type == MMAD_SRC_U8 ? 2 : 4) == 0,
+                   "%s: %s is not aligned to a pair of its elements", who, s[i].name);
+    const float lo = range_in[2 * i], hi = range_in[2 * i + 1];
+    // hi == lo (or a NaN): no map to [-1, 1] exists
+    MMAD_CHECK_ARG(hi > lo || hi < lo, "%s: range_in of %s is empty (lo=%g hi=%g)", who, s[i].name, (double)lo,
+                   (double)hi);
+    g.lo[i] = lo;
+    g.span[i] = (float)((double)hi - (double)lo);   // norm_vec's r_in, rounded once
+  }
+  return MMAD_OK;
+}
+
+int mmad_hsr_fuse_raw_check(int n, const void* r, int r_type, const void* d, int d_type, const float* t,
+                            const float* m, const float* range_in, const float* weights, int unimodal,
+                            const float* out, int ld_out) {
+  HsrOffsets off;
+  HsrRanges g;
+  return hsr_raw_check(n, r, r_type, d, d_type, t, m, range_in, weights, unimodal, out, ld_out, off, g);
+}
+
+int mmad_hsr_fuse_raw(int n, const void* r, int r_type, const void* d, int d_type, const float* t,
+                      const float* m, float r_lo, float r_hi, float d_lo, float d_hi, float t_lo, float t_hi,
+                      const float* weights, int unimodal, float* out, int ld_out, void* stream) {
+  const float range_in[6] = {r_lo, r_hi, d_lo, d_hi, t_lo, t_hi};
+  return mmad_hsr_fuse_raw_launch(n, r, r_type, d, d_type, t, m, range_in, 0, weights, unimodal, out, ld_out,
+                                  stream);
+}
+
+int mmad_hsr_fuse_raw_launch(int n, const void* r, int r_type, const void* d, int d_type, const float* t,
+                             const float* m, const float* range_in, int rcp, const float* weights, int unimodal,
+                             float* out, int ld_out, void* stream) {
+  HsrOffsets off;
+  HsrRanges g;
+  RET_IF_HSR(hsr_raw_check(n, r, r_type, d, d_type, t, m, range_in, weights, unimodal, out, ld_out, off, g));
+  if (rcp)
+    for (int i = 0; i < 3; ++i)
+      if (g.span[i] != 0.f) g.inv[i] = 1.f / g.span[i];   // fp32, rounded once on the host
+  if (n == 0) return MMAD_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const bool r8 = off.r >= 0 && r_type == MMAD_SRC_U8, d8 = off.d >= 0 && d_type == MMAD_SRC_U8;
+  const uint8_t *rb = (const uint8_t*)r, *db = (const uint8_t*)d;
+  const float *rf = (const float*)r, *df = (const float*)d;
+  if (r8 && d8) hsr_fuse_raw_k<<<n, 256, 0, s>>>(rb, db, t, m, g, weights, out, ld_out, off);
+  else if (r8) hsr_fuse_raw_k<<<n, 256, 0, s>>>(rb, df, t, m, g, weights, out, ld_out, off);
+  else if (d8) hsr_fuse_raw_k<<<n, 256, 0, s>>>(rf, db, t, m, g, weights, out, ld_out, off);
+  else hsr_fuse_raw_k<<<n, 256, 0, s>>>(rf, df, t, m, g, weights, out, ld_out, off);
   MMAD_LAUNCH_CHECK();
   return MMAD_OK;
 }

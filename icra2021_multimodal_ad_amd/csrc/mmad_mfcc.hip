@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "mmad_common.h"
+#include "mmad_ops.h"
 
 namespace {
 
@@ -337,9 +338,21 @@ int64_t mmad_mfcc_ws_bytes(int64_t n_frames, int n_mels) {
   return (ws_doubles(n_frames, n_mels) * 8 + 255) / 256 * 256;
 }
 
-int mmad_mfcc(const void* pcm, int pcm_type, int64_t L, int sr, int n_fft, int n_mels, int n_mfcc,
-              const void* plan, int64_t plan_bytes, float* out, int64_t keep, float lo, float hi, float* norm_out,
-              void* ws, int64_t ws_bytes, void* stream) {
+// the launch shape of F frames: 128-thread blocks while they all fit on the
+// chip's 256 CUs at once (one block a CU at n_fft 4410: LDS), 256-thread
+// blocks beyond
+struct PowerGrid { int owned, threads, chunks; };
+static PowerGrid power_grid(int64_t F, int n_fft) {
+  PowerGrid g;
+  g.owned = (n_fft & 1) ? n_fft / 2 + 1 : n_fft / 4 + 1;
+  g.threads = F * ((g.owned + 127) / 128) > 256 ? 256 : 128;
+  g.chunks = (g.owned + g.threads - 1) / g.threads;
+  return g;
+}
+
+int mmad_mfcc_check(const void* pcm, int pcm_type, int64_t L, int sr, int n_fft, int n_mels, int n_mfcc,
+                    const void* plan, int64_t plan_bytes, const float* out, int64_t keep,
+                    const float* norm_out, const void* ws, int64_t ws_bytes) {
   MMAD_CHECK_ARG(params_ok(sr, n_fft, n_mels, n_mfcc),
                  "mfcc: bad parameters (sr=%d n_fft=%d n_mels=%d n_mfcc=%d; n_fft 16..4410, n_mels 1..128, "
                  "n_mfcc 1..n_mels)", sr, n_fft, n_mels, n_mfcc);
@@ -356,13 +369,21 @@ int mmad_mfcc(const void* pcm, int pcm_type, int64_t L, int sr, int n_fft, int n
   const PlanLayout pl = plan_layout(n_fft, n_mels, n_mfcc);
   MMAD_CHECK_ARG(plan_bytes >= pl.bytes, "mfcc: plan of %lld bytes, needs %lld", (long long)plan_bytes,
                  (long long)pl.bytes);
-  const int owned = (n_fft & 1) ? n_fft / 2 + 1 : n_fft / 4 + 1;
-  // 128-thread blocks while they all fit on the chip's 256 CUs at once (one
-  // block a CU at n_fft 4410: LDS), 256-thread blocks beyond
-  int threads = 128;
-  if (F * ((owned + 127) / 128) > 256) threads = 256;
-  const int chunks = (owned + threads - 1) / threads;
-  MMAD_CHECK_ARG(F * chunks < (1LL << 31), "mfcc: %lld frames are too many for one call", (long long)F);
+  MMAD_CHECK_ARG(F * power_grid(F, n_fft).chunks < (1LL << 31), "mfcc: %lld frames are too many for one call",
+                 (long long)F);
+  return MMAD_OK;
+}
+
+int mmad_mfcc(const void* pcm, int pcm_type, int64_t L, int sr, int n_fft, int n_mels, int n_mfcc,
+              const void* plan, int64_t plan_bytes, float* out, int64_t keep, float lo, float hi, float* norm_out,
+              void* ws, int64_t ws_bytes, void* stream) {
+  const int rc = mmad_mfcc_check(pcm, pcm_type, L, sr, n_fft, n_mels, n_mfcc, plan, plan_bytes, out, keep, norm_out,
+                                 ws, ws_bytes);
+  if (rc != MMAD_OK) return rc;
+  const int64_t F = mmad_mfcc_frames(L, n_fft);
+  const PlanLayout pl = plan_layout(n_fft, n_mels, n_mfcc);
+  const PowerGrid pg = power_grid(F, n_fft);
+  const int owned = pg.owned, threads = pg.threads, chunks = pg.chunks;
 
   PlanView v;
   const double* base = (const double*)plan;

@@ -89,6 +89,23 @@ struct MmadGroupSq {
 };
 int mmad_group_sq_launch(const MmadGroupSq& a, void* stream);
 
+// ---- the refusals of mmad_mfcc and mmad_hsr_fuse_raw on their own: the
+// entry points' argument lists without the stream (range_in: r, d, t as
+// (lo, hi) pairs), nothing launched.  mmad_ae_online_tick runs them ahead of
+// its first launch; the entry points themselves start with them.
+int mmad_mfcc_check(const void* pcm, int pcm_type, int64_t L, int sr, int n_fft, int n_mels, int n_mfcc,
+                    const void* plan, int64_t plan_bytes, const float* out, int64_t keep,
+                    const float* norm_out, const void* ws, int64_t ws_bytes);
+int mmad_hsr_fuse_raw_check(int n, const void* r, int r_type, const void* d, int d_type, const float* t,
+                            const float* m, const float* range_in, const float* weights, int unimodal,
+                            const float* out, int ld_out);
+// mmad_hsr_fuse_raw with the ranges as an array and the tick's norm_rcp
+// (include/mmad.h, mmad_tick_args): rcp != 0 multiplies by fl(1 / (hi - lo))
+// where the entry point divides
+int mmad_hsr_fuse_raw_launch(int n, const void* r, int r_type, const void* d, int d_type, const float* t,
+                             const float* m, const float* range_in, int rcp, const float* weights, int unimodal,
+                             float* out, int ld_out, void* stream);
+
 #define MMAD_MAX_REDUCE_JOBS 24
 struct MmadReduceJob {
   const float* src;   // partials, row i at src + i*stride

@@ -632,6 +632,14 @@ class NativeAE:
              groups_state.numel() - (galigned - gbase) if groups_state is not None else 0)
         return out
 
+    def online_tick(self, args, graph=True):
+        """One sensor tick from device-resident raw buffers to scores
+        (mmad_ae_online_tick): args a _native.TickArgs whose buffers the caller
+        keeps alive (online.OnlineScorer.bind_sensors fills one, once).  With
+        graph=True a repeated call replays one captured hipGraph."""
+        self.sync_shadow()
+        call("mmad_ae_online_tick", self._h, ctypes.byref(args), 1 if graph else 0, stream_ptr())
+
     def diff_widths(self):
         return [self.enc_widths[0]] + self.enc_widths[1:]
 

@@ -78,8 +78,10 @@ class HSR_Net(nn.Module):
             raise ValueError(f"HSR_Net.modality_columns: unimodal module with config.sensor={sensor!r}")
         return modality_columns(sensor)
 
-    def packed_weights(self):
-        """fp32 [mmad_hsr_weight_count()] on the module's device (conv1r w, b, ...)."""
+    def packed_weights(self, out=None):
+        """fp32 [mmad_hsr_weight_count()] on the module's device (conv1r w, b, ...).
+        ``out`` (optional): a contiguous fp32 vector of that length to pack
+        into instead of a new one (a buffer a captured graph reads); returned."""
         parts = []
         for name in _PACKED:
             conv = getattr(self, name)
@@ -88,7 +90,11 @@ class HSR_Net(nn.Module):
         n = _native.load().mmad_hsr_weight_count()
         if w.numel() != n:
             raise _native.NativeError(f"hsr weights: packed {w.numel()} floats, kernel expects {n}")
-        return w
+        if out is None:
+            return w
+        if out.dtype != torch.float32 or out.dim() != 1 or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"HSR_Net.packed_weights: out must be a contiguous fp32 vector of {n}")
+        return out.copy_(w)
 
     def forward(self, r, d, l, t, m, out=None):
         """Fuse ``config.slicing_size`` windows (data_loaders.py:183-229).

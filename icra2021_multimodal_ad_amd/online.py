@@ -18,7 +18,15 @@ row), from one more launch in the same graph (mmad_ae_online_score_groups).
 The ranges are CONTIGUOUS: each starts where the one before it ends (the
 operator takes ascending bounds); a caller who wants a gap names the gap as a
 group of its own and ignores its row.
+
+``bind_sensors`` / ``tick`` run a whole sensor tick -- raw queues to scores --
+as one host-to-device copy and one replayed graph (mmad_ae_online_tick: the
+MFCC launches, mmad_hsr_fuse_raw with norm_vec folded into its loads, the
+pass above).  ``score_sensors`` stays the route for a microphone queue that is
+still filling (DESIGN.md §4 "Sensor tick in one graph").
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -49,6 +57,31 @@ def group_bounds(groups, width):
     if bounds[0] < 0 or bounds[-1] > width:
         raise ValueError(f"OnlineScorer: groups span [{bounds[0]}, {bounds[-1]}) outside the {width} input columns")
     return tuple(n for n, _ in items), bounds
+
+
+_reciprocal = {}
+
+
+def device_divides_by_reciprocal(device):
+    """Whether torch on ``device`` computes fp32 ``tensor / python_scalar`` as
+    the product with the rounded reciprocal of the scalar (its device kernels
+    do; the quotients of 0, 2, .., 510 by 255 tell: 126 of the 256 are one ulp
+    off the division), False when it is the IEEE quotient.  Probed once a device;
+    normalised_sensors goes through that operator, so ``bind_sensors`` has the
+    tick's kernel form the quotient the same way."""
+    device = torch.device(device)
+    if device not in _reciprocal:
+        v = 2 * np.arange(256, dtype=np.float32)
+        got = (torch.from_numpy(v).to(device) / 255).cpu().numpy()
+        ieee, rcp = v / np.float32(255), v * (np.float32(1) / np.float32(255))
+        if np.array_equal(got, ieee):
+            _reciprocal[device] = False
+        elif np.array_equal(got, rcp):
+            _reciprocal[device] = True
+        else:
+            raise RuntimeError("device_divides_by_reciprocal: torch's fp32 division by a scalar is neither the "
+                               "quotient nor the reciprocal product on this device; set OnlineScorer.norm_division")
+    return _reciprocal[device]
 
 
 def rows_for(n_windows):
@@ -147,13 +180,16 @@ class OnlineScorer:
         return thr
 
     def _run(self, B):
-        n_enc = self.nat.n_enc
         grouped = {} if self.groups is None else dict(
             groups=self.groups, group_out=self.group_out, group_flags=self.group_flags,
             group_thresholds=self.group_thresholds, groups_state=self.groups_state)
         self.nat.online_score(self.x, B, self.out, self.state, flags=self.flags,
                               thresholds=self.thresholds, start=self.start, end=self.end,
                               rows=self.rows, **grouped)
+        return self._results(B)
+
+    def _results(self, B):
+        n_enc = self.nat.n_enc
         res = {"layer_sq": self.out[:n_enc + 1, :B], "base": self.out[n_enc + 1, :B],
                "sap": self.out[n_enc + 2, :B],
                "nap": self.out[n_enc + 3, :B] if self.nap is not None else None,
@@ -209,6 +245,154 @@ class OnlineScorer:
         r, d, t = normalised_sensors(force_q, hand_q, depth_q, dev)
         m = self.front_end.latest(mic_pcm, int(hsr_net.batch_size))[1]
         return self.score_frames(hsr_net, r, d, t, m)
+
+    # ---- the sensor tick as one replayed graph (mmad_ae_online_tick) ---------
+    _tick = None         # bind_sensors' buffers and argument struct
+    # norm_vec's quotient inside the tick, read by bind_sensors: 'ieee' (a
+    # correctly rounded division, mmad_hsr_fuse_raw's), 'reciprocal' (the
+    # product with fl(1 / (hi - lo))), or None: whichever of the two torch's
+    # elementwise kernels compute on the scorer's device, so that ``tick``
+    # returns score_sensors' bits (device_divides_by_reciprocal)
+    norm_division = None
+
+    def bind_sensors(self, hsr_net, mic_samples, hand_dtype=np.uint8, depth_dtype=np.uint8, front_end=None):
+        """Fix the shapes of ``tick``: the fused ``hsr_net`` (its
+        ``batch_size`` = B <= rows windows a tick), a microphone queue of
+        exactly ``mic_samples`` int16 samples, and the camera queues' element
+        types (uint8 or float32).  Allocates one pinned host staging buffer
+        and its device twin -- PCM int16 [mic_samples] | hand [B][3072] |
+        depth [B][1024] | force fp32 [B], every segment 256-byte aligned --
+        the MFCC outputs, the front end's workspace at its final size and the
+        HSR weights, packed once (``refresh_sensors`` repacks them).
+        front_end: an MfccFrontEnd (None: ``self.front_end``, else the
+        reference's 44.1 kHz / 0.1 s / 128 mel / 13 settings)."""
+        from . import _native
+        from .data_loaders import mic_front_end
+        B = int(hsr_net.batch_size)
+        if B > self.rows:
+            raise ValueError(f"OnlineScorer.bind_sensors: slicing_size {B} > {self.rows}; score_windows "
+                             "(reconstruction_aggregation) is the batch route")
+        if hsr_net.unimodal:
+            raise ValueError("OnlineScorer.bind_sensors: the tick fuses all four streams (a fused HSR_Net)")
+        kinds = {np.dtype(np.uint8): _native.SRC_U8, np.dtype(np.float32): _native.SRC_F32}
+        hand_dtype, depth_dtype = np.dtype(hand_dtype), np.dtype(depth_dtype)
+        if hand_dtype not in kinds or depth_dtype not in kinds:
+            raise ValueError(f"OnlineScorer.bind_sensors: hand / depth of {hand_dtype} / {depth_dtype} (uint8 or float32)")
+        dev = self.x.device
+        fe = front_end or self.front_end or mic_front_end(device=dev)
+        self.front_end = fe
+        L = int(mic_samples)
+        F = fe.frames(L)
+        if F < B:
+            raise ValueError(f"OnlineScorer.bind_sensors: {L} samples are {max(F, 0)} frames < the {B} windows of a tick")
+        if fe.n_mfcc != 13 or self.x.shape[1] != 1728:
+            raise ValueError("OnlineScorer.bind_sensors: the fused row takes 13 MFCCs and a 1728-wide model")
+        # the staging layout: name -> (byte offset, dtype, shape)
+        seg, off = {}, 0
+        for name, dt, shape in (("pcm", np.dtype(np.int16), (L,)), ("hand", hand_dtype, (B, 3072)),
+                                ("depth", depth_dtype, (B, 1024)), ("force", np.dtype(np.float32), (B,))):
+            seg[name] = (off, dt, shape)
+            off = (off + int(np.prod(shape)) * dt.itemsize + 255) // 256 * 256
+        host = torch.zeros(off, dtype=torch.uint8).pin_memory()
+        raw = torch.zeros(off, dtype=torch.uint8, device=dev)
+        flat = host.numpy()
+        views = {k: flat[o:o + int(np.prod(s)) * dt.itemsize].view(dt).reshape(s) for k, (o, dt, s) in seg.items()}
+        lib = _native.load()
+        t = dict(B=B, L=L, net=hsr_net, host=host, raw=raw, views=views, copied=torch.cuda.Event(),
+                 mfcc=torch.zeros((F, 13), device=dev), norm=torch.zeros((B, 13), device=dev),
+                 ws=torch.zeros(int(lib.mmad_mfcc_ws_bytes(F, fe.n_mels)), dtype=torch.uint8, device=dev),
+                 weights=torch.zeros(int(lib.mmad_hsr_weight_count()), device=dev))
+        hsr_net.packed_weights(out=t["weights"])
+        a, ptr = _native.TickArgs(), (lambda v: v.data_ptr())
+        base = raw.data_ptr()
+        a.pcm, a.pcm_type, a.L = base + seg["pcm"][0], _native.PCM_I16, L
+        a.r, a.r_type = base + seg["hand"][0], kinds[hand_dtype]
+        a.d, a.d_type = base + seg["depth"][0], kinds[depth_dtype]
+        a.t = base + seg["force"][0]
+        a.range_in[:] = [0, 255, 0, 255, 0, 400]        # normalised_sensors' ranges
+        how = self.norm_division or ("reciprocal" if device_divides_by_reciprocal(dev) else "ieee")
+        if how not in ("ieee", "reciprocal"):
+            raise ValueError(f"OnlineScorer.norm_division={how!r} ('ieee', 'reciprocal' or None)")
+        a.norm_rcp = int(how == "reciprocal")
+        a.sr, a.n_fft, a.n_mels, a.n_mfcc = fe.params
+        a.plan, a.plan_bytes = ptr(fe.plan), fe.plan.numel()
+        a.mfcc_out, a.mfcc_out_bytes = ptr(t["mfcc"]), t["mfcc"].numel() * 4
+        a.mfcc_norm, a.mfcc_norm_bytes = ptr(t["norm"]), t["norm"].numel() * 4
+        a.mfcc_ws, a.mfcc_ws_bytes = ptr(t["ws"]), t["ws"].numel()
+        a.hsr_weights, a.hsr_weight_count = ptr(t["weights"]), t["weights"].numel()
+        a.x, a.ld_x, a.B, a.rows = ptr(self.x), self.x.stride(0), B, self.rows
+        a.sap_start, a.sap_end = self.start, self.end
+        a.thresholds, a.out, a.flags = ptr(self.thresholds), ptr(self.out), ptr(self.flags)
+
+        def aligned(buf):
+            p = (buf.data_ptr() + 255) // 256 * 256
+            return p, buf.numel() - (p - buf.data_ptr())
+        a.state, a.state_bytes = aligned(self.state)
+        if self.groups is not None:
+            t["bounds"] = (ctypes.c_int * len(self.groups))(*self.groups)
+            a.bounds, a.G = t["bounds"], len(self.groups) - 1
+            a.group_thresholds, a.group_out = ptr(self.group_thresholds), ptr(self.group_out)
+            a.group_flags = ptr(self.group_flags)
+            a.gstate, a.gstate_bytes = aligned(self.groups_state)
+        t["args"] = a
+        self._tick = t
+        return self
+
+    def refresh_sensors(self):
+        """Repack the bound HSR_Net's weights into the buffer the tick's graph
+        reads, after its parameters changed: the next ``tick`` sees them, no
+        new capture."""
+        if self._tick is None:
+            raise ValueError("OnlineScorer.refresh_sensors: call bind_sensors first")
+        self._tick["net"].packed_weights(out=self._tick["weights"])
+
+    def tick(self, force_q, hand_q, depth_q, mic_q):
+        """``score_sensors`` on the shapes ``bind_sensors`` fixed, as one
+        host-to-device copy and one graph launch: the queues are written into
+        the pinned staging buffer with numpy (the first B frames of force,
+        hand and depth, as HSR_Net.forward takes them; all of mic_q: int16
+        samples or the reference's list of ``bytes`` chunks), copied over on
+        the current stream, and mmad_ae_online_tick replays MFCC -> fusion ->
+        scoring.  Returns what ``score_sensors`` returns."""
+        t = self._tick
+        if t is None:
+            raise ValueError("OnlineScorer.tick: call bind_sensors first")
+        B, L, v = t["B"], t["L"], t["views"]
+        if isinstance(mic_q, (bytes, bytearray, memoryview)):
+            mic_q = [mic_q]
+        chunks = isinstance(mic_q, (list, tuple)) and (not mic_q or isinstance(mic_q[0], (bytes, bytearray, memoryview)))
+        if chunks:
+            n_mic = sum(len(c) for c in mic_q) // 2
+        else:
+            mic_q = np.asarray(mic_q).reshape(-1)
+            if mic_q.dtype != np.int16:
+                raise ValueError(f"OnlineScorer.tick: PCM of dtype {mic_q.dtype} (the staging buffer holds int16)")
+            n_mic = mic_q.size
+        if n_mic != L:
+            raise ValueError(f"OnlineScorer.tick: a mic queue of {n_mic} samples, bound to {L}; score_sensors takes "
+                             "a queue that is still filling")
+        qs = {}
+        for name, q in (("force", force_q), ("hand", hand_q), ("depth", depth_q)):
+            q = np.asarray(q)
+            q = q.reshape(q.shape[0], -1) if q.ndim > 1 else q.reshape(-1, 1)
+            if q.shape[0] < B:
+                raise ValueError(f"OnlineScorer.tick: {name} queue of {q.shape[0]} frames < the {B} windows of a tick")
+            if q.shape[1] != v[name].reshape(B, -1).shape[1]:
+                raise ValueError(f"OnlineScorer.tick: {name} frames of {q.shape[1]} values")
+            if v[name].dtype == np.uint8 and q.dtype != np.uint8:
+                raise ValueError(f"OnlineScorer.tick: {name} queue of {q.dtype}, bound as uint8")
+            qs[name] = q[:B]
+        t["copied"].synchronize()            # the last tick's copy has read the staging buffer
+        if chunks:
+            np.copyto(v["pcm"], np.frombuffer(b"".join(mic_q), dtype=np.int16))
+        else:
+            np.copyto(v["pcm"], mic_q)
+        for name, q in qs.items():
+            np.copyto(v[name].reshape(B, -1), q, casting="same_kind")
+        t["raw"].copy_(t["host"], non_blocking=True)
+        t["copied"].record()
+        self.nat.online_tick(t["args"])
+        return self._results(B)
 
     def close(self):
         """Detach the fit from the model."""

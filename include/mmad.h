@@ -1021,6 +1021,82 @@ int mmad_mfcc(const void* pcm, int pcm_type, int64_t L, int sr, int n_fft, int n
               const void* plan, int64_t plan_bytes, float* out, int64_t keep, float lo, float hi,
               float* norm_out, void* ws, int64_t ws_bytes, void* stream);
 
+/* mmad_hsr_fuse on the sensor queues as they are: r [n][3072] and d [n][1024]
+ * of element type r_type / d_type (MMAD_SRC_U8 or MMAD_SRC_F32: the camera
+ * queues' uint8 frames, or fp32), t fp32 [n], each mapped inside the loads by
+ * norm_vec (utils/data_loaders.py:703-712) from its (lo, hi) range to [-1, 1]
+ * -- fp32, every operation rounded on its own, ((2 (v - lo)) / (hi - lo)) + (-1)
+ * with a correctly rounded division and no contraction, hi - lo formed in
+ * double and rounded once: the bits of the elementwise chain in IEEE fp32
+ * followed by mmad_hsr_fuse.  m fp32 [n][13] is taken as it is (mmad_mfcc's
+ * norm_out).  weights, unimodal, the nullable modalities, out and ld_out as
+ * mmad_hsr_fuse (columns past the row width are not written); one launch.
+ * MMAD_EINVAL, nothing launched: every refusal of mmad_hsr_fuse, and for a
+ * modality the call reads: an element type other than U8 / F32, hi == lo, a
+ * pointer not aligned to two of its elements (the u8 loads are 2-byte pairs). */
+int mmad_hsr_fuse_raw(int n, const void* r, int r_type, const void* d, int d_type, const float* t,
+                      const float* m, float r_lo, float r_hi, float d_lo, float d_hi, float t_lo,
+                      float t_hi, const float* weights, int unimodal, float* out, int ld_out,
+                      void* stream);
+
+/* One tick of the deployment loop from device-resident raw buffers to scores:
+ * mmad_mfcc's three launches (pcm [L] -> mfcc_out [n_frames][n_mfcc] and
+ * mfcc_norm [B][n_mfcc], the last B frames to [-1, 1]), mmad_hsr_fuse_raw of
+ * r, d, t and mfcc_norm (the fused row, range_in = r, d, t as (lo, hi) pairs)
+ * into x [B][ld_x], then the online pass on x: mmad_ae_online_score (rows 16)
+ * or mmad_ae_online_score64 (rows 64), or with bounds != NULL
+ * mmad_ae_online_score_groups.  out, flags and the group outputs are the bits
+ * those entry points produce on the same x.  norm_rcp: 0 = the quotient of
+ * mmad_hsr_fuse_raw (IEEE division); != 0 = the product with fl(1 / (hi - lo)),
+ * rounded once, in its place -- what torch's device kernels compute for
+ * tensor / Python scalar, so that a tick reproduces, bit for bit, a row that
+ * was normalised by torch on the device (OnlineScorer.score_sensors); the
+ * two differ in the last place of about half the uint8 values.  It is part of
+ * the graph signature.  The arguments travel in one flat
+ * struct; every buffer is caller-owned device memory with the alignment its
+ * own entry point asks for, and the sizes are checked against
+ * mmad_mfcc_plan_bytes, mmad_mfcc_ws_bytes, mmad_mfcc_frames * n_mfcc * 4
+ * (mfcc_out_bytes), B * n_mfcc * 4 (mfcc_norm_bytes), mmad_hsr_weight_count
+ * (hsr_weight_count), mmad_ae_online_state_bytes[64] and
+ * mmad_ae_online_groups_bytes.
+ * use_graph != 0: the first call for a signature -- the online pass's own plus
+ * the sensor pointers and types, L, the MFCC parameters, plan, workspace and
+ * outputs, the weight buffer and the ranges -- runs eagerly and captures one
+ * linear chain on one stream; later calls are one hipGraphLaunch.  The
+ * captures share the handle's 8 online graphs (mmad_ae_graph_count,
+ * mmad_ae_clear_graphs).  Every buffer is read at replay time: new samples,
+ * frames or repacked weights in the same buffers need no new capture.
+ * MMAD_EINVAL, nothing launched and nothing captured: a null argument struct,
+ * a model input width other than the fused row's 1728, mfcc_out / mfcc_norm /
+ * hsr_weights too small, and every refusal of mmad_mfcc, mmad_hsr_fuse_raw and
+ * the online entry point the call selects. */
+typedef struct mmad_tick_args {
+  /* the raw queues */
+  const void* pcm; int pcm_type; int64_t L;
+  const void* r; int r_type;
+  const void* d; int d_type;
+  const float* t;
+  float range_in[6];
+  int norm_rcp;
+  /* the microphone front end */
+  int sr, n_fft, n_mels, n_mfcc;
+  const void* plan; int64_t plan_bytes;
+  float* mfcc_out; int64_t mfcc_out_bytes;
+  float* mfcc_norm; int64_t mfcc_norm_bytes;
+  void* mfcc_ws; int64_t mfcc_ws_bytes;
+  /* the fusion producer */
+  const float* hsr_weights; int hsr_weight_count;
+  /* the online pass */
+  float* x; int ld_x, B, rows, sap_start, sap_end;
+  const float* thresholds; float* out; uint8_t* flags;
+  void* state; int64_t state_bytes;
+  /* per-modality scores (bounds == NULL: none) */
+  const int* bounds; int G;
+  const float* group_thresholds; float* group_out; uint8_t* group_flags;
+  void* gstate; int64_t gstate_bytes;
+} mmad_tick_args;
+int mmad_ae_online_tick(mmad_ae* h, const mmad_tick_args* a, int use_graph, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,14 @@ once (AE weights + the encoder again + V^T) / 8 TB/s.
       (64 rows), both handles, with the fit (d0 read from the NAP operand) and
       without (d0 into the groups buffer); groups = the fused row's modality
       columns scaled to the model's D.  The grouped pass is one dependent
-      launch more; a difference inside the 3 % spread decides nothing."""
+      launch more; a difference inside the 3 % spread decides nothing.
+  python tools/online_latency.py --tick [--out profiles/online_tick_latency.json]
+      the sensor tick in one graph (OnlineScorer.tick: one host-to-device copy
+      and one replay of mmad_ae_online_tick) against score_sensors on the same
+      scorer and the same raw queues, alternated call by call in one process:
+      10 windows on 16 rows and 32 windows on 64 rows, the 1728-wide 3-layer
+      fp32 model with the modality groups.  The baseline is the score_sensors
+      of the same run; a GPU-time ratio inside 1 +- 3 % is no gain."""
 import argparse
 import ctypes
 import json
@@ -274,6 +281,57 @@ def run_groups(dtype):
     return bounds, cases
 
 
+TICK_CASES = ((10, 16), (32, 64))   # (windows a tick, row capacity)
+
+
+def run_tick(B, rows):
+    """OnlineScorer.tick (one copy + one graph launch, mmad_ae_online_tick)
+    against score_sensors on the same scorer and queues, call by call."""
+    from icra2021_multimodal_ad_amd.hsr_net import HSR_Net
+    from icra2021_multimodal_ad_amd.model_builder import get_model
+    from icra2021_multimodal_ad_amd.online import OnlineScorer
+    torch.manual_seed(7)
+    net = HSR_Net(False, types.SimpleNamespace(slicing_size=B, batch_size=B, gpu_id=0)).cuda()
+    torch.manual_seed(8)
+    model = get_model(types.SimpleNamespace(input_size=1728, btl_size=16, n_layers=3, gpu_id=0, dtype="f32",
+                                            models="ae"))
+    rng = np.random.Generator(np.random.PCG64(81))
+    hand_q = rng.integers(0, 256, size=(B, 32 * 32 * 3)).astype(np.uint8)
+    depth_q = rng.integers(0, 256, size=(B, 32 * 32)).astype(np.uint8)
+    force_q = rng.uniform(0, 400, size=B)
+    pcm = rng.integers(-8000, 8000, size=(B + 1) * 4410 - 2205).astype(np.int16)   # B + 1 frames
+    sc = OnlineScorer(model, rows=rows, groups=net.modality_columns())
+    sc.bind_sensors(net, len(pcm))
+    q = (force_q, hand_q, depth_q, pcm)
+    keep = lambda r: {k: v.clone() for k, v in r.items() if v is not None}   # noqa: E731
+    a, b = keep(sc.tick(*q)), keep(sc.score_sensors(net, *q))
+    same_bits = all(torch.equal(a[k], b[k]) for k in a)
+    rel = float(((a["base"] - b["base"]).abs().max() / b["base"].abs().max()).item())
+    res = measure({"score_sensors": lambda: sc.score_sensors(net, *q), "tick": lambda: sc.tick(*q)})
+    for kind in ("gpu", "wall"):
+        s, t = res["score_sensors"][kind], res["tick"][kind]
+        res[f"tick_minus_score_sensors_{kind}_us"] = t["median_us"] - s["median_us"]
+        res[f"tick_vs_score_sensors_{kind}"] = t["median_us"] / s["median_us"]
+    res.update(B=B, rows=rows, pcm_samples=len(pcm), tick_equals_score_sensors_bits=same_bits,
+               base_max_rel_diff=rel, tick_host_calls="1 copy_ + 1 hipGraphLaunch")
+    print(f"tick B={B} rows={rows}", {k: (round(v["gpu"]["median_us"], 1), round(v["wall"]["median_us"], 1))
+                                     for k, v in res.items() if isinstance(v, dict) and "gpu" in v},
+          f"bits equal: {same_bits}", flush=True)
+    return res
+
+
+def main_tick(out):
+    cases = {f"f32_B{B}_rows{rows}": run_tick(B, rows) for B, rows in TICK_CASES}
+    doc = {"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "calls": CALLS, "spread": SPREAD,
+           "model": "input 1728, btl 16, 3 layers, fp32, groups = the fused row's modality columns",
+           "cases": cases,
+           "gpu_gain_outside_spread": {k: c["tick_vs_score_sensors_gpu"] for k, c in cases.items()
+                                       if c["tick_vs_score_sensors_gpu"] < 1 - SPREAD}}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+
+
 def main_groups(out):
     cases = {}
     for dt in ("f32", "bf16"):
@@ -313,8 +371,11 @@ def main():
     ap.add_argument("--variant", default=None)
     ap.add_argument("--rows64", action="store_true")
     ap.add_argument("--groups", action="store_true")
+    ap.add_argument("--tick", action="store_true")
     a = ap.parse_args()
     _native.require_gpu()
+    if a.tick:
+        return main_tick(a.out or "profiles/online_tick_latency.json")
     if a.rows64:
         return main_rows64(a.out or "profiles/online_rows64_latency.json")
     if a.groups:
