@@ -4,7 +4,7 @@ kernels index differently: a batch that ends inside a 32-row statistics
 chunk, inside / at / one past a 128-row slab, widths at 63 / 64 / 65 of a
 column slab.
 
-    mmad_pack_input, mmad_unpack_output        bit-exact against torch
+    mmad_pack_input, mmad_unpack_output        bit-exact against torch (also the split-bf16 planes)
     mmad_bn_train_apply, mmad_bn_eval_affine   float64 from the input itself
     mmad_bn_act_bwd (reduce + apply)           float64, bounds of test_gpu_bn_apply.py
     mmad_act_bwd, mmad_colsum                  exact dz, float64 column sums
@@ -31,6 +31,8 @@ pytestmark = pytest.mark.gpu
 PAIRS = [(2, 1), (31, 63), (32, 64), (33, 65), (127, 128), (128, 130), (129, 1), (200, 65), (128, 64),
          (33, 130)]
 DTYPES = {"f32": (_native.F32, torch.float32), "bf16": (_native.BF16, torch.bfloat16)}
+# pack / unpack also have a split-bf16 form: two bf16 planes [2][Mp][Kp], hi = RNE(x), lo = RNE(x - hi)
+PACK_DTYPES = list(DTYPES) + ["x3"]
 ACTS = ["leakyrelu", "relu", "sigmoid", "tanh"]
 SLOPE = 0.2
 ROW_SENTINEL = 3.0
@@ -87,11 +89,18 @@ def _pack_sources(M, K):
     return [("vector", r4, 0), ("ld_x>K", r4 + 8, 0), ("ld_x%4", odd, 0), ("offset", r4 + 4, 1)]
 
 
-@pytest.mark.parametrize("dtype", list(DTYPES))
+def _planes_of(x):
+    hi = x.bfloat16()
+    return torch.stack((hi, (x - hi.float()).bfloat16()))
+
+
+@pytest.mark.parametrize("dtype", PACK_DTYPES)
 @pytest.mark.parametrize("M,K", PAIRS)
 def test_pack_input_is_torch_rounding(M, K, dtype):
     """out[:M, :K] is x.to(dtype) bit for bit (RNE for bf16, a copy for fp32),
-    everything else of [Mp][Kp] is 0."""
+    everything else of [Mp][Kp] is 0.  x3: both planes of [2][Mp][Kp]."""
+    if dtype == "x3":
+        return _pack_planes_case(M, K)
     dt, td = DTYPES[dtype]
     Mp, Kp = pad(M), pad(K)
     for name, ld_x, off in _pack_sources(M, K):
@@ -114,9 +123,35 @@ def test_pack_input_is_torch_rounding(M, K, dtype):
         assert (out[M:] == 0).all() and (out[:, K:] == 0).all(), name
 
 
-@pytest.mark.parametrize("dtype", list(DTYPES))
+def _pack_planes_case(M, K):
+    """the x3 form on the sources and special values of the test above"""
+    Mp, Kp = pad(M), pad(K)
+    for name, ld_x, off in _pack_sources(M, K):
+        g = _gen(M, K, ld_x, off)
+        flat = torch.randn(off + M * ld_x + GUARD, generator=g) * 3
+        ties = torch.tensor([1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -(1 + 2.0 ** -8), 2.0 ** -130, -0.0, 65280.0])
+        flat[off:off + min(6, M * ld_x)] = ties[:min(6, M * ld_x)]
+        x = flat[off:off + M * ld_x].view(M, ld_x)
+        dflat = flat.cuda()
+        src = dflat[off:]
+        assert (src.data_ptr() % 16 == 0) == (off == 0)
+        out = torch.full((2, Mp, Kp), NAN, dtype=torch.bfloat16, device="cuda")
+        call("mmad_pack_input", _native.BF16X3, M, K, Mp, Kp, ptr(src), ld_x, ptr(out), stream_ptr())
+        torch.cuda.synchronize()
+        out = out.cpu()
+        want = _planes_of(x[:, :K].contiguous())
+        assert torch.equal(_bits(out[0, :M, :K]), _bits(want[0])), name
+        assert torch.equal(_bits(out[1, :M, :K]), _bits(want[1])), name
+        assert (out[:, M:] == 0).all() and (out[:, :, K:] == 0).all(), name
+
+
+@pytest.mark.parametrize("dtype", PACK_DTYPES)
 @pytest.mark.parametrize("M,N", PAIRS)
 def test_unpack_output_writes_only_the_valid_region(M, N, dtype):
+    """x3: out = float(hi) + float(lo) bit for bit, the lo plane at
+    roundup(M, 128) * Np elements."""
+    if dtype == "x3":
+        return _unpack_planes_case(M, N)
     dt, td = DTYPES[dtype]
     Mp, Np, ld_out = pad(M), pad(N), N + 3
     y = torch.full((Mp, Np), NAN, dtype=td)
@@ -128,6 +163,21 @@ def test_unpack_output_writes_only_the_valid_region(M, N, dtype):
     out = out.cpu()
     body = out[:M * ld_out].view(M, ld_out)
     assert torch.equal(_bits(body[:, :N]), _bits(y[:M, :N].float()))
+    assert (body[:, N:] == SENTINEL).all() and (out[M * ld_out:] == SENTINEL).all()
+
+
+def _unpack_planes_case(M, N):
+    Mp, Np, ld_out = pad(M), pad(N), N + 3
+    y = torch.full((2, Mp, Np), NAN, dtype=torch.bfloat16)
+    y[:, :M, :N] = _planes_of(torch.randn(M, N, generator=_gen(M, N)) * 3)
+    assert (y[1, :M, :N] != 0).any()
+    out = torch.full((M * ld_out + GUARD,), SENTINEL, device="cuda")
+    yd = y.cuda()
+    call("mmad_unpack_output", _native.BF16X3, M, N, Np, ptr(yd), ptr(out), ld_out, stream_ptr())
+    torch.cuda.synchronize()
+    out = out.cpu()
+    body = out[:M * ld_out].view(M, ld_out)
+    assert torch.equal(_bits(body[:, :N]), _bits(y[0, :M, :N].float() + y[1, :M, :N].float()))
     assert (body[:, N:] == SENTINEL).all() and (out[M * ld_out:] == SENTINEL).all()
 
 
