@@ -51,6 +51,35 @@ class TickArgs(ctypes.Structure):
     ]
 
 
+MAX_BANK = 8     # MMAD_MAX_BANK: members of one mmad_fc_rows_group call / one sensor bank
+
+
+class FcRowsDesc(ctypes.Structure):
+    """mmad_fc_rows_desc (include/mmad.h), field for field."""
+    _fields_ = [
+        ("dtype", _I), ("M", _I), ("N", _I), ("K", _I), ("Np", _I), ("Kp", _I),
+        ("x", _P), ("w", _P), ("bias", _P),
+        ("act", _I), ("slope", _F),
+        ("bn_scale", _P), ("bn_shift", _P),
+        ("y", _P),
+        ("ref", _P), ("ref_dtype", _I), ("ldref", _I),
+        ("diff", _P), ("lddiff", _I),
+        ("colw", _P), ("rowsq", _P),
+    ]
+
+
+class BankMember(ctypes.Structure):
+    """mmad_bank_member (include/mmad.h), field for field."""
+    _fields_ = [
+        ("sap_start", _I), ("sap_end", _I),
+        ("thresholds", _P), ("out", _P), ("flags", _P),
+        ("state", _P), ("state_bytes", _I64),
+        ("bounds", ctypes.POINTER(_I)), ("G", _I),
+        ("group_thresholds", _P), ("group_out", _P), ("group_flags", _P),
+        ("gstate", _P), ("gstate_bytes", _I64),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/mmad.h one-to-one
 SIGNATURES = {
     "mmad_last_error_string": (ctypes.c_char_p, []),
@@ -190,6 +219,14 @@ SIGNATURES = {
     "mmad_mfcc": (_I, [_P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _I64, _F, _F, _P, _P, _I64, _P]),
     "mmad_hsr_fuse_raw": (_I, [_I, _P, _I, _P, _I, _P, _P, _F, _F, _F, _F, _F, _F, _P, _I, _P, _I, _P]),
     "mmad_ae_online_tick": (_I, [_P, ctypes.POINTER(TickArgs), _I, _P]),
+    "mmad_fc_rows_group": (_I, [_I, _I, ctypes.POINTER(FcRowsDesc), _P]),
+    "mmad_online_bank_create": (_I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), ctypes.POINTER(_I), _I]),
+    "mmad_online_bank_destroy": (None, [_P]),
+    "mmad_online_bank_state_bytes": (_I64, [_P, _I]),
+    "mmad_online_bank_score": (_I, [_P, _P, _I, _I, ctypes.POINTER(BankMember), _I, _P]),
+    "mmad_online_bank_tick": (_I, [_P, ctypes.POINTER(TickArgs), ctypes.POINTER(BankMember), _I, _P]),
+    "mmad_online_bank_graph_nodes": (_I, [_P]),
+    "mmad_online_bank_graph_count": (_I, [_P]),
 }
 
 

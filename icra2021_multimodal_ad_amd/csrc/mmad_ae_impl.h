@@ -454,17 +454,18 @@ struct GraphCaptureResult {
   int rc;
   hipError_t err;
 };
+// the capture itself, on *gstream (created on first use); kernel_nodes, if
+// given, receives the captured graph's kernel-node count
 template <class Pass>
-GraphCaptureResult capture_graph(mmad_ae* h, Pass pass, hipGraphExec_t* exec) {
+GraphCaptureResult capture_graph_on(hipStream_t* gstream, Pass pass, hipGraphExec_t* exec,
+                                    int* kernel_nodes = nullptr) {
   *exec = nullptr;
-  hipError_t e = h->gstream ? hipSuccess : hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal);
+  hipError_t e = *gstream ? hipSuccess : hipStreamCreateWithFlags(gstream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamBeginCapture(*gstream, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) return {GC_BEGIN, MMAD_OK, e};
-  h->capturing = true;
-  const int rc = pass(h->gstream);
-  h->capturing = false;
+  const int rc = pass(*gstream);
   hipGraph_t graph = nullptr;
-  e = hipStreamEndCapture(h->gstream, &graph);
+  e = hipStreamEndCapture(*gstream, &graph);
   if (e == hipSuccess && !graph) e = hipErrorUnknown;
   GraphCaptureResult res{GC_OK, rc, e};
   if (rc != MMAD_OK) {
@@ -474,7 +475,26 @@ GraphCaptureResult capture_graph(mmad_ae* h, Pass pass, hipGraphExec_t* exec) {
   } else if ((res.err = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0)) != hipSuccess) {
     res.stage = GC_INSTANTIATE;
   }
+  if (graph && kernel_nodes && res.stage == GC_OK) {
+    size_t nn = 0;
+    *kernel_nodes = 0;
+    if (hipGraphGetNodes(graph, nullptr, &nn) == hipSuccess && nn) {
+      std::vector<hipGraphNode_t> nodes(nn);
+      if (hipGraphGetNodes(graph, nodes.data(), &nn) == hipSuccess)
+        for (size_t i = 0; i < nn; ++i) {
+          hipGraphNodeType t;
+          if (hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel) ++*kernel_nodes;
+        }
+    }
+  }
   if (graph) (void)hipGraphDestroy(graph);
+  return res;
+}
+template <class Pass>
+GraphCaptureResult capture_graph(mmad_ae* h, Pass pass, hipGraphExec_t* exec) {
+  h->capturing = true;
+  const GraphCaptureResult res = capture_graph_on(&h->gstream, pass, exec);
+  h->capturing = false;
   return res;
 }
 // the score / online policy: the failed stage's error is the call's (the

@@ -73,6 +73,37 @@ struct MmadOnlineFinish {
 };
 int mmad_online_finish(const MmadOnlineFinish& f, int rows, void* stream);
 
+// ---- grouped forms (the sensor bank, mmad_online_bank_*): one launch over up
+// to MMAD_MAX_BANK members, each member's bits those of the single form above.
+// A block finds its member in a prefix table of per-member block counts that
+// travels by value in the kernel arguments; no atomics, no wait between blocks.
+// dtype[i]: MMAD_F32 / MMAD_BF16; members of one element type share a launch
+// (at most two launches); a[i].N == 0: the member owns no blocks here
+int mmad_skinny_group_launch(int rows, int n, const int* dtype, const MmadSkinny* a, void* stream);
+struct MmadPackMember {
+  int dtype, K, Kp;      // MMAD_F32 / MMAD_BF16
+  const float* x;        // [M][ld_x]; 16-byte aligned rows or not (vec, set by the launcher)
+  void* out;             // [rows][Kp]
+};
+int mmad_pack_input_group(int n, int M, int rows, int ld_x, const MmadPackMember* m, void* stream);
+// all members' BN layers in one table: member i owns layers [first[i], first[i + 1])
+#define MMAD_BANK_MAX_BN 64
+struct MmadOnlineFoldMember {
+  const float *params, *running;
+  float *scale, *shift;
+  float eps;
+  int n_bn;
+};
+struct MmadOnlineFoldGroup {
+  int n;
+  int first[MMAD_MAX_BANK + 1];
+  MmadOnlineFoldMember m[MMAD_MAX_BANK];
+  int bn_off[MMAD_BANK_MAX_BN], N[MMAD_BANK_MAX_BN];
+  int64_t g_off[MMAD_BANK_MAX_BN], be_off[MMAD_BANK_MAX_BN];
+};
+int mmad_online_fold_group(const MmadOnlineFoldGroup& g, void* stream);
+int mmad_online_finish_group(int n, const MmadOnlineFinish* f, int rows, void* stream);
+
 // ---- column-group mean squares (mmad_group_sq, mmad_group.hip): the bounds
 // travel in the argument struct.  n_flag: rows >= n_flag get flag 0 whatever
 // their score (the online pass's padding rows; the C-ABI form sets it to N)

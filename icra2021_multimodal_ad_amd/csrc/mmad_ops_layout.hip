@@ -7,13 +7,12 @@ namespace {
 // u*256 + tid): every chunk's loads are issued before the first conversion,
 // PU x V/4 16-B loads in flight per thread
 template <typename T, int PU>
-__global__ void pack_input_k(int M, int K, int Mp, int Kp, const float* __restrict__ x, int ldx,
-                             int vec, T* __restrict__ out, const MmadDyn* __restrict__ dyn) {
+__device__ __forceinline__ void pack_chunks(int M, int K, int Mp, int Kp, const float* __restrict__ x, int ldx,
+                                            int vec, T* __restrict__ out, int block) {
   constexpr int V = Vec<T>::N;
-  if (dyn) x = dyn->x;
   const int cpr = Kp / V;
   const int64_t total = (int64_t)Mp * cpr;
-  const int64_t base = (int64_t)blockIdx.x * blockDim.x * PU + threadIdx.x;
+  const int64_t base = (int64_t)block * blockDim.x * PU + threadIdx.x;
   floatx4 f[PU][V / 4];
   bool full[PU];
 #pragma unroll
@@ -45,6 +44,33 @@ __global__ void pack_input_k(int M, int K, int Mp, int Kp, const float* __restri
     }
     *(uint4v*)(out + (size_t)row * Kp + c0) = r;
   }
+}
+template <typename T, int PU>
+__global__ void pack_input_k(int M, int K, int Mp, int Kp, const float* __restrict__ x, int ldx,
+                             int vec, T* __restrict__ out, const MmadDyn* __restrict__ dyn) {
+  if (dyn) x = dyn->x;
+  pack_chunks<T, PU>(M, K, Mp, Kp, x, ldx, vec, out, blockIdx.x);
+}
+
+// mmad_pack_input_group: member i packs its columns of the shared rows with
+// the blocks [first[i], first[i + 1]), each by its own element type
+struct PackGroup {
+  int n, M, Mp, ldx;
+  int first[MMAD_MAX_BANK + 1];
+  int vec[MMAD_MAX_BANK];
+  MmadPackMember m[MMAD_MAX_BANK];
+};
+template <int PU>
+__global__ void pack_input_group_k(const PackGroup g) {
+  const int b = blockIdx.x;
+  if (b >= g.first[g.n]) return;
+  int i = 0;
+  while (b >= g.first[i + 1]) ++i;
+  const MmadPackMember& m = g.m[i];
+  if (m.dtype == MMAD_BF16)
+    pack_chunks<bf16, PU>(g.M, m.K, g.Mp, m.Kp, m.x, g.ldx, g.vec[i], (bf16*)m.out, b - g.first[i]);
+  else
+    pack_chunks<float, PU>(g.M, m.K, g.Mp, m.Kp, m.x, g.ldx, g.vec[i], (float*)m.out, b - g.first[i]);
 }
 
 // MMAD_BF16X3 producers: fp32 -> the (hi, lo) bf16 planes
@@ -171,6 +197,26 @@ int mmad_pack_input_dyn(int dtype, int M, int K, int Mp, int Kp, const float* x,
 int mmad_pack_input(int dtype, int M, int K, int Mp, int Kp, const float* x, int ld_x, void* out,
                     void* stream) {
   return mmad_pack_input_dyn(dtype, M, K, Mp, Kp, x, ld_x, out, nullptr, stream);
+}
+
+int mmad_pack_input_group(int n, int M, int rows, int ld_x, const MmadPackMember* m, void* stream) {
+  MMAD_CHECK_ARG(n >= 1 && n <= MMAD_MAX_BANK && m, "pack_input_group: n=%d outside 1..%d", n, MMAD_MAX_BANK);
+  MMAD_CHECK_ARG(M <= rows, "pack_input_group: bad sizes");
+  PackGroup g{};
+  g.n = n; g.M = M; g.Mp = rows; g.ldx = ld_x;
+  for (int i = 0; i < n; ++i) {
+    MMAD_CHECK_ARG(m[i].dtype == MMAD_F32 || m[i].dtype == MMAD_BF16, "pack_input_group: bad dtype %d",
+                   m[i].dtype);
+    MMAD_CHECK_ARG(m[i].K <= m[i].Kp && m[i].Kp % 8 == 0 && ld_x >= m[i].K && m[i].x && m[i].out,
+                   "pack_input_group: bad sizes");
+    g.m[i] = m[i];
+    g.vec[i] = ((uintptr_t)m[i].x % 16 == 0 && ld_x % 4 == 0) ? 1 : 0;
+    const int V = m[i].dtype == MMAD_BF16 ? Vec<bf16>::N : Vec<float>::N;
+    g.first[i + 1] = g.first[i] + (int)nblk((int64_t)rows * (m[i].Kp / V), 256 * 4);
+  }
+  pack_input_group_k<4><<<g.first[n], 256, 0, (hipStream_t)stream>>>(g);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
 }
 
 int mmad_split_planes(int64_t n, const float* src, void* hi, void* lo, void* stream) {

@@ -85,15 +85,17 @@ __device__ __forceinline__ void mma(floatx4 (&acc)[RT], const floatx4 (&a)[RT][U
         acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][u][j], b[u][j], acc[t], 0, 0, 0);
 }
 
+// one block's work: the 16 output columns of tile `tile` of a (the body of
+// skinny_k, and of skinny_group_k for the member the block belongs to)
 template <typename T, int RT, int ROWS>
-__global__ __launch_bounds__(NW * 64) void skinny_k(const MmadSkinny a) {
+__device__ __forceinline__ void skinny_tile(const MmadSkinny& a, const int tile) {
   typedef typename Frag<T>::V V;
   constexpr int KL = Frag<T>::KL;   // k per lane and load
   constexpr int CK = 4 * KL * U;    // k per chunk: 128 (bf16) / 64 (fp32) = 256 bytes of a row
   __shared__ floatx4 red[NW][RT][64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int c16 = lane & 15, g = lane >> 4;
-  const int n0 = blockIdx.x * 16;
+  const int n0 = tile * 16;
   const T* wp = (const T*)a.w + (size_t)(n0 + c16) * a.Kp + g * KL;
   const T* xp = (const T*)a.x + (size_t)c16 * a.Kp + g * KL;
   const size_t xt = (size_t)16 * a.Kp;   // one row tile of x
@@ -176,10 +178,51 @@ __global__ __launch_bounds__(NW * 64) void skinny_k(const MmadSkinny a) {
       for (int r = 0; r < 4; ++r) {
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) sq[r] += __shfl_xor(sq[r], o);
-        if (c16 == 0) a.rowsq[(size_t)blockIdx.x * ROWS + 16 * t + 4 * g + r] = sq[r];
+        if (c16 == 0) a.rowsq[(size_t)tile * ROWS + 16 * t + 4 * g + r] = sq[r];
       }
     }
   }
+}
+
+template <typename T, int RT, int ROWS>
+__global__ __launch_bounds__(NW * 64) void skinny_k(const MmadSkinny a) {
+  skinny_tile<T, RT, ROWS>(a, blockIdx.x);
+}
+
+// mmad_fc_rows_group: the members of one element type in one grid.  Member i
+// owns the blocks [first[i], first[i + 1]) -- its 16-column tiles in order;
+// the walk over the table is block-uniform, the member's arguments are scalar
+// loads from the kernel arguments
+struct SkinnyGroup {
+  int n;
+  int first[MMAD_MAX_BANK + 1];
+  MmadSkinny m[MMAD_MAX_BANK];
+};
+template <typename T, int RT, int ROWS>
+__global__ __launch_bounds__(NW * 64) void skinny_group_k(const SkinnyGroup g) {
+  const int b = blockIdx.x;
+  if (b >= g.first[g.n]) return;
+  int i = 0;
+  while (b >= g.first[i + 1]) ++i;
+  skinny_tile<T, RT, ROWS>(g.m[i], b - g.first[i]);
+}
+
+// eval-BN (scale, shift) of one BN element: j of the [n_bn] running-stat
+// layout, its layer found among the n layers of (bn_off, N, g_off, be_off)
+__device__ __forceinline__ void fold_elem(const int j, const int n, const int n_bn, const int* bn_off,
+                                          const int* N, const int64_t* g_off, const int64_t* be_off,
+                                          const float* __restrict__ params, const float* __restrict__ running,
+                                          const float eps, float* __restrict__ scale, float* __restrict__ shift) {
+  int i = 0;
+  while (i + 1 < n && j >= bn_off[i + 1]) ++i;
+  const int c = j - bn_off[i];
+  float s = 0.f, t = 0.f;
+  if (c < N[i]) {
+    s = params[g_off[i] + c] * (float)(1.0 / sqrt((double)running[n_bn + j] + (double)eps));
+    t = params[be_off[i] + c] - running[j] * s;
+  }
+  scale[j] = s;
+  shift[j] = t;
 }
 
 // eval-BN (scale, shift) of every BN layer in one grid (mmad_bn_eval_affine
@@ -189,23 +232,29 @@ __global__ __launch_bounds__(256) void online_fold_k(const MmadOnlineFold f, con
                                                      float* __restrict__ scale, float* __restrict__ shift) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= f.n_bn) return;
+  fold_elem(j, f.n, f.n_bn, f.bn_off, f.N, f.g_off, f.be_off, params, running, eps, scale, shift);
+}
+
+// ... of every member of a bank: blk[i] .. blk[i + 1] are member i's blocks
+struct FoldGroupBlocks { int blk[MMAD_MAX_BANK + 1]; };
+__global__ __launch_bounds__(256) void online_fold_group_k(const MmadOnlineFoldGroup g, const FoldGroupBlocks p) {
+  const int b = blockIdx.x;
+  if (b >= p.blk[g.n]) return;
   int i = 0;
-  while (i + 1 < f.n && j >= f.bn_off[i + 1]) ++i;
-  const int c = j - f.bn_off[i];
-  float s = 0.f, t = 0.f;
-  if (c < f.N[i]) {
-    s = params[f.g_off[i] + c] * (float)(1.0 / sqrt((double)running[f.n_bn + j] + (double)eps));
-    t = params[f.be_off[i] + c] - running[j] * s;
-  }
-  scale[j] = s;
-  shift[j] = t;
+  while (b >= p.blk[i + 1]) ++i;
+  const MmadOnlineFoldMember& m = g.m[i];
+  const int j = (b - p.blk[i]) * 256 + threadIdx.x;
+  if (j >= m.n_bn) return;
+  const int l0 = g.first[i];
+  fold_elem(j, g.first[i + 1] - l0, m.n_bn, g.bn_off + l0, g.N + l0, g.g_off + l0, g.be_off + l0, m.params,
+            m.running, m.eps, m.scale, m.shift);
 }
 
 // one block of 512: the row partials summed in tile order (left to right, 8
 // loads at a time, per (layer, row)), then BASE / SAP / NAP and flags.
 // rs [tiles][ROWS], out [n_diff + 3][ROWS], flags [3][ROWS]
 template <int ROWS>
-__global__ __launch_bounds__(512) void online_finish_k(const MmadOnlineFinish f) {
+__device__ __forceinline__ void online_finish_body(const MmadOnlineFinish& f) {
   __shared__ float lsq[MMAD_ONLINE_MAX_DIFF + 1][ROWS];
   const int b = threadIdx.x % ROWS;
   for (int j = threadIdx.x / ROWS; j < f.n_diff + (f.nap_rs ? 1 : 0); j += 512 / ROWS) {
@@ -250,6 +299,16 @@ __global__ __launch_bounds__(512) void online_finish_k(const MmadOnlineFinish f)
     f.flags[2 * ROWS + b] = (th && f.nap_rs) ? (uint8_t)(nap > th[2]) : 0;
   }
 }
+template <int ROWS>
+__global__ __launch_bounds__(512) void online_finish_k(const MmadOnlineFinish f) {
+  online_finish_body<ROWS>(f);
+}
+// one block per member of a bank
+struct FinishGroup { MmadOnlineFinish f[MMAD_MAX_BANK]; };
+template <int ROWS>
+__global__ __launch_bounds__(512) void online_finish_group_k(const FinishGroup g) {
+  online_finish_body<ROWS>(g.f[blockIdx.x]);
+}
 
 template <typename T>
 void launch(const MmadSkinny& a, hipStream_t s) {
@@ -266,28 +325,34 @@ void launch(const MmadSkinny& a, hipStream_t s) {
   }
 }
 
-// mmad_fc_rows16 / mmad_fc_rows64: the C-ABI arguments into MmadSkinny
-int fc_rows(int rows, int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
-            const float* bias, int act, float slope, const float* bn_scale, const float* bn_shift, void* y,
-            const void* ref, int ref_dtype, int ldref, float* diff, int lddiff, const float* colw,
-            float* rowsq, void* stream) {
-  MMAD_CHECK_ARG(K >= 1 && K <= Kp, "fc_rows%d: K=%d outside 1..Kp=%d", rows, K, Kp);
-  MMAD_CHECK_ARG(!bn_scale == !bn_shift, "fc_rows%d: bn_scale and bn_shift go together", rows);
-  MMAD_CHECK_ARG(!ref || ((ref_dtype == MMAD_F32 || ref_dtype == dtype) && ldref >= N),
-                 "fc_rows%d: ref is fp32 or the operand dtype, ldref >= N", rows);
-  MMAD_CHECK_ARG(!diff || lddiff >= N, "fc_rows%d: lddiff < N", rows);
-  MmadSkinny a{};
-  a.rows = rows; a.M = M; a.N = N; a.Np = Np; a.Kp = Kp;
-  a.x = x; a.w = w; a.bias = bias; a.act = act; a.slope = slope;
-  a.scale = bn_scale; a.shift = bn_shift; a.y = y;
-  a.ref = ref; a.ref_f32 = ref_dtype == MMAD_F32; a.ldref = ldref;
-  a.diff = diff; a.lddiff = lddiff; a.colw = colw; a.rowsq = rowsq;
-  return mmad_skinny_launch(dtype, a, stream);
+// the members of element type T (mask bit i) as one launch, all on RT row tiles
+template <typename T>
+void launch_group(int rows, int n, unsigned mask, const MmadSkinny* a, hipStream_t s) {
+  SkinnyGroup g{};
+  int maxM = 1;
+  for (int i = 0; i < n; ++i) {
+    g.first[i + 1] = g.first[i];
+    if (!(mask >> i & 1)) continue;
+    g.m[i] = a[i];
+    g.first[i + 1] += a[i].Np / 16;
+    maxM = a[i].M > maxM ? a[i].M : maxM;
+  }
+  g.n = n;
+  const dim3 grid(g.first[n]), block(NW * 64);
+  if (rows == 16) {
+    skinny_group_k<T, 1, 16><<<grid, block, 0, s>>>(g);
+    return;
+  }
+  switch ((maxM + 15) / 16) {
+    case 1: skinny_group_k<T, 1, 64><<<grid, block, 0, s>>>(g); break;
+    case 2: skinny_group_k<T, 2, 64><<<grid, block, 0, s>>>(g); break;
+    case 3: skinny_group_k<T, 3, 64><<<grid, block, 0, s>>>(g); break;
+    default: skinny_group_k<T, 4, 64><<<grid, block, 0, s>>>(g); break;
+  }
 }
 
-}  // namespace
-
-int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream) {
+// every refusal of the operator, nothing launched
+int skinny_check(int dtype, const MmadSkinny& a) {
   const int R = a.rows;
   MMAD_CHECK_ARG(R == 16 || R == 64, "fc_rows: rows=%d (16 or 64)", R);
   MMAD_CHECK_ARG(dtype == MMAD_F32 || dtype == MMAD_BF16, "fc_rows%d: dtype %d (MMAD_F32 or MMAD_BF16)", R, dtype);
@@ -303,12 +368,88 @@ int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream) {
     mmad_set_error("fc_rows%d: activation %d has no per-element epilogue", R, a.act);
     return MMAD_EUNSUPPORTED;
   }
+  return MMAD_OK;
+}
+
+// the C-ABI arguments' own refusals (mmad_fc_rows16 / 64, a descriptor of
+// mmad_fc_rows_group), then MmadSkinny
+int fc_rows_args(int rows, int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
+                 const float* bias, int act, float slope, const float* bn_scale, const float* bn_shift, void* y,
+                 const void* ref, int ref_dtype, int ldref, float* diff, int lddiff, const float* colw,
+                 float* rowsq, MmadSkinny& a) {
+  MMAD_CHECK_ARG(K >= 1 && K <= Kp, "fc_rows%d: K=%d outside 1..Kp=%d", rows, K, Kp);
+  MMAD_CHECK_ARG(!bn_scale == !bn_shift, "fc_rows%d: bn_scale and bn_shift go together", rows);
+  MMAD_CHECK_ARG(!ref || ((ref_dtype == MMAD_F32 || ref_dtype == dtype) && ldref >= N),
+                 "fc_rows%d: ref is fp32 or the operand dtype, ldref >= N", rows);
+  MMAD_CHECK_ARG(!diff || lddiff >= N, "fc_rows%d: lddiff < N", rows);
+  a = MmadSkinny{};
+  a.rows = rows; a.M = M; a.N = N; a.Np = Np; a.Kp = Kp;
+  a.x = x; a.w = w; a.bias = bias; a.act = act; a.slope = slope;
+  a.scale = bn_scale; a.shift = bn_shift; a.y = y;
+  a.ref = ref; a.ref_f32 = ref_dtype == MMAD_F32; a.ldref = ldref;
+  a.diff = diff; a.lddiff = lddiff; a.colw = colw; a.rowsq = rowsq;
+  return MMAD_OK;
+}
+
+// mmad_fc_rows16 / mmad_fc_rows64
+int fc_rows(int rows, int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
+            const float* bias, int act, float slope, const float* bn_scale, const float* bn_shift, void* y,
+            const void* ref, int ref_dtype, int ldref, float* diff, int lddiff, const float* colw,
+            float* rowsq, void* stream) {
+  MmadSkinny a;
+  const int rc = fc_rows_args(rows, dtype, M, N, K, Np, Kp, x, w, bias, act, slope, bn_scale, bn_shift, y, ref,
+                              ref_dtype, ldref, diff, lddiff, colw, rowsq, a);
+  return rc != MMAD_OK ? rc : mmad_skinny_launch(dtype, a, stream);
+}
+
+}  // namespace
+
+int mmad_skinny_launch(int dtype, const MmadSkinny& a, void* stream) {
+  const int rc = skinny_check(dtype, a);
+  if (rc != MMAD_OK) return rc;
   if (dtype == MMAD_BF16)
     launch<bf16>(a, (hipStream_t)stream);
   else
     launch<float>(a, (hipStream_t)stream);
   MMAD_LAUNCH_CHECK();
   return MMAD_OK;
+}
+
+int mmad_skinny_group_launch(int rows, int n, const int* dtype, const MmadSkinny* a, void* stream) {
+  MMAD_CHECK_ARG(n >= 1 && n <= MMAD_MAX_BANK, "fc_rows_group: n=%d outside 1..%d", n, MMAD_MAX_BANK);
+  MMAD_CHECK_ARG(rows == 16 || rows == 64, "fc_rows_group: rows=%d (16 or 64)", rows);
+  MMAD_CHECK_ARG(dtype && a, "fc_rows_group: null members");
+  unsigned mask[2] = {0, 0};   // members by element type; N == 0: in neither
+  for (int i = 0; i < n; ++i) {
+    if (a[i].N == 0) continue;
+    MMAD_CHECK_ARG(a[i].rows == rows, "fc_rows_group: member %d of %d rows in a call of %d", i, a[i].rows, rows);
+    const int rc = skinny_check(dtype[i], a[i]);
+    if (rc != MMAD_OK) return rc;
+    mask[dtype[i] == MMAD_BF16] |= 1u << i;
+  }
+  if (mask[0]) launch_group<float>(rows, n, mask[0], a, (hipStream_t)stream);
+  if (mask[1]) launch_group<bf16>(rows, n, mask[1], a, (hipStream_t)stream);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
+int mmad_fc_rows_group(int rows, int n, const mmad_fc_rows_desc* d, void* stream) {
+  MMAD_CHECK_ARG(n >= 1 && n <= MMAD_MAX_BANK, "fc_rows_group: n=%d outside 1..%d", n, MMAD_MAX_BANK);
+  MMAD_CHECK_ARG(rows == 16 || rows == 64, "fc_rows_group: rows=%d (16 or 64)", rows);
+  MMAD_CHECK_ARG(d, "fc_rows_group: null descriptors");
+  MmadSkinny a[MMAD_MAX_BANK];
+  int dt[MMAD_MAX_BANK];
+  for (int i = 0; i < n; ++i) {
+    const mmad_fc_rows_desc& m = d[i];
+    a[i] = MmadSkinny{};
+    dt[i] = m.dtype;
+    if (m.N == 0) continue;
+    const int rc = fc_rows_args(rows, m.dtype, m.M, m.N, m.K, m.Np, m.Kp, m.x, m.w, m.bias, m.act, m.slope,
+                                m.bn_scale, m.bn_shift, m.y, m.ref, m.ref_dtype, m.ldref, m.diff, m.lddiff,
+                                m.colw, m.rowsq, a[i]);
+    if (rc != MMAD_OK) return rc;
+  }
+  return mmad_skinny_group_launch(rows, n, dt, a, stream);
 }
 
 int mmad_fc_rows16(int dtype, int M, int N, int K, int Np, int Kp, const void* x, const void* w,
@@ -342,6 +483,35 @@ int mmad_online_finish(const MmadOnlineFinish& f, int rows, void* stream) {
     online_finish_k<16><<<1, 512, 0, (hipStream_t)stream>>>(f);
   else
     online_finish_k<64><<<1, 512, 0, (hipStream_t)stream>>>(f);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
+int mmad_online_fold_group(const MmadOnlineFoldGroup& g, void* stream) {
+  MMAD_CHECK_ARG(g.n >= 1 && g.n <= MMAD_MAX_BANK && g.first[g.n] <= MMAD_BANK_MAX_BN,
+                 "online_fold_group: %d members, %d BatchNorm layers (at most %d, %d)", g.n,
+                 g.n >= 1 && g.n <= MMAD_MAX_BANK ? g.first[g.n] : 0, MMAD_MAX_BANK, MMAD_BANK_MAX_BN);
+  FoldGroupBlocks p{};
+  for (int i = 0; i < g.n; ++i) p.blk[i + 1] = p.blk[i] + (g.m[i].n_bn + 255) / 256;
+  if (p.blk[g.n] == 0) return MMAD_OK;
+  online_fold_group_k<<<p.blk[g.n], 256, 0, (hipStream_t)stream>>>(g, p);
+  MMAD_LAUNCH_CHECK();
+  return MMAD_OK;
+}
+
+int mmad_online_finish_group(int n, const MmadOnlineFinish* f, int rows, void* stream) {
+  MMAD_CHECK_ARG(n >= 1 && n <= MMAD_MAX_BANK && f, "online_finish_group: n=%d outside 1..%d", n, MMAD_MAX_BANK);
+  MMAD_CHECK_ARG(rows == 16 || rows == 64, "online_finish_group: rows=%d (16 or 64)", rows);
+  FinishGroup g{};
+  for (int i = 0; i < n; ++i) {
+    MMAD_CHECK_ARG(f[i].n_diff >= 1 && f[i].n_diff <= MMAD_ONLINE_MAX_DIFF,
+                   "online_finish_group: member %d has %d diff layers", i, f[i].n_diff);
+    g.f[i] = f[i];
+  }
+  if (rows == 16)
+    online_finish_group_k<16><<<n, 512, 0, (hipStream_t)stream>>>(g);
+  else
+    online_finish_group_k<64><<<n, 512, 0, (hipStream_t)stream>>>(g);
   MMAD_LAUNCH_CHECK();
   return MMAD_OK;
 }

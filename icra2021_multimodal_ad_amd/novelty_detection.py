@@ -207,6 +207,31 @@ class NoveltyDetecter:
             scorer.calibrate(valid)
         return scorer
 
+    def online_bank(self, models, train_x, valid_x, rows=None):
+        """The fused detector and its unimodal siblings as one
+        online.SensorBank: ``models`` maps config.sensor names ('All',
+        'hand_camera', 'head_depth', 'force_torque', 'mic') to trained models
+        (one per ``--sensor`` setting, 1..8 of them; each of this detecter's
+        ``config`` layer settings).  Every member's scorer is built by
+        ``online_scorer`` on that sensor's columns of the fused rows
+        ``train_x`` / ``valid_x`` [N, 1728] -- its own NAP fit and calibrated
+        thresholds -- and the bank scores them all from one shared row per
+        tick, sharing launches (DESIGN.md §4 "Sensor bank").  The bank shares
+        one fused HSR_Net: the unimodal models are expected to have been
+        trained on that network's blocks of the fused row."""
+        from .hsr_net import FUSED_WIDTH, modality_columns
+        from .online import SENSOR_KEYS, SensorBank
+        cols = modality_columns()
+        scorers, starts = {}, {}
+        for name, model in models.items():
+            if name not in SENSOR_KEYS:
+                raise ValueError(f"online_bank: unknown sensor {name!r} ({', '.join(SENSOR_KEYS)})")
+            c0, c1 = (0, FUSED_WIDTH) if SENSOR_KEYS[name] is None else cols[SENSOR_KEYS[name]]
+            tx, vx = (torch.as_tensor(v).reshape(len(v), -1)[:, c0:c1].contiguous() for v in (train_x, valid_x))
+            scorers[name] = self.online_scorer(model, tx, vx, rows=rows)
+            starts[name] = c0
+        return SensorBank(scorers, starts, width=FUSED_WIDTH)
+
     def test(self, model, dset_manager, train_loader, valid_loader, test_loader, df_test=None):
         """novelty_detection.py:15-85.  Returns ((base_auroc, base_aupr),
         (sap_auroc, sap_aupr), (nap_auroc, nap_aupr), df_test) with df_test a

@@ -93,6 +93,136 @@ def rows_for(n_windows):
     return 64 if 16 < int(n_windows or 0) <= 64 else ROWS
 
 
+def _aligned(buf):
+    """(256-byte aligned address inside ``buf``, the bytes left from there)."""
+    p = (buf.data_ptr() + 255) // 256 * 256
+    return p, buf.numel() - (p - buf.data_ptr())
+
+
+def _member_args(sc, a, keep):
+    """One scorer's pass arguments -- SAP range, thresholds, outputs, state and
+    groups -- into ``a``: a TickArgs (OnlineScorer.bind_sensors) or a
+    BankMember (SensorBank); the two name these fields alike.  keep: a dict
+    that holds the ctypes bounds array alive."""
+    a.sap_start, a.sap_end = sc.start, sc.end
+    a.thresholds, a.out, a.flags = sc.thresholds.data_ptr(), sc.out.data_ptr(), sc.flags.data_ptr()
+    a.state, a.state_bytes = _aligned(sc.state)
+    if sc.groups is not None:
+        keep["bounds"] = (ctypes.c_int * len(sc.groups))(*sc.groups)
+        a.bounds, a.G = keep["bounds"], len(sc.groups) - 1
+        a.group_thresholds, a.group_out = sc.group_thresholds.data_ptr(), sc.group_out.data_ptr()
+        a.group_flags = sc.group_flags.data_ptr()
+        a.gstate, a.gstate_bytes = _aligned(sc.groups_state)
+
+
+def _bind_front(who, x, rows, hsr_net, mic_samples, hand_dtype, depth_dtype, front_end, norm_division,
+                fused_model=False):
+    """What OnlineScorer.bind_sensors and SensorBank.bind_sensors share: the
+    checks, the staging layout (PCM int16 [mic_samples] | hand [B][3072] | depth
+    [B][1024] | force fp32 [B], every segment 256-byte aligned), its pinned
+    host buffer and device twin, the MFCC buffers, the packed HSR weights, the
+    ``norm_division`` probe, and a TickArgs with the front end, the fusion
+    producer and the fused row's destination ``x`` [rows, >= 1728] filled in.
+    fused_model: the caller's model reads the whole row (x must be 1728 wide)."""
+    from . import _native
+    from .data_loaders import mic_front_end
+    B = int(hsr_net.batch_size)
+    if B > rows:
+        raise ValueError(f"{who}.bind_sensors: slicing_size {B} > {rows}; score_windows "
+                         "(reconstruction_aggregation) is the batch route")
+    if hsr_net.unimodal:
+        raise ValueError(f"{who}.bind_sensors: the tick fuses all four streams (a fused HSR_Net)")
+    kinds = {np.dtype(np.uint8): _native.SRC_U8, np.dtype(np.float32): _native.SRC_F32}
+    hand_dtype, depth_dtype = np.dtype(hand_dtype), np.dtype(depth_dtype)
+    if hand_dtype not in kinds or depth_dtype not in kinds:
+        raise ValueError(f"{who}.bind_sensors: hand / depth of {hand_dtype} / {depth_dtype} (uint8 or float32)")
+    dev = x.device
+    fe = front_end or mic_front_end(device=dev)
+    L = int(mic_samples)
+    F = fe.frames(L)
+    if F < B:
+        raise ValueError(f"{who}.bind_sensors: {L} samples are {max(F, 0)} frames < the {B} windows of a tick")
+    if fe.n_mfcc != 13 or (x.shape[1] != 1728 if fused_model else x.shape[1] < 1728):
+        raise ValueError(f"{who}.bind_sensors: the fused row takes 13 MFCCs and a 1728-wide model")
+    # the staging layout: name -> (byte offset, dtype, shape)
+    seg, off = {}, 0
+    for name, dt, shape in (("pcm", np.dtype(np.int16), (L,)), ("hand", hand_dtype, (B, 3072)),
+                            ("depth", depth_dtype, (B, 1024)), ("force", np.dtype(np.float32), (B,))):
+        seg[name] = (off, dt, shape)
+        off = (off + int(np.prod(shape)) * dt.itemsize + 255) // 256 * 256
+    host = torch.zeros(off, dtype=torch.uint8).pin_memory()
+    raw = torch.zeros(off, dtype=torch.uint8, device=dev)
+    flat = host.numpy()
+    views = {k: flat[o:o + int(np.prod(s)) * dt.itemsize].view(dt).reshape(s) for k, (o, dt, s) in seg.items()}
+    lib = _native.load()
+    t = dict(B=B, L=L, net=hsr_net, host=host, raw=raw, views=views, copied=torch.cuda.Event(), front_end=fe,
+             mfcc=torch.zeros((F, 13), device=dev), norm=torch.zeros((B, 13), device=dev),
+             ws=torch.zeros(int(lib.mmad_mfcc_ws_bytes(F, fe.n_mels)), dtype=torch.uint8, device=dev),
+             weights=torch.zeros(int(lib.mmad_hsr_weight_count()), device=dev))
+    hsr_net.packed_weights(out=t["weights"])
+    a, ptr = _native.TickArgs(), (lambda v: v.data_ptr())
+    base = raw.data_ptr()
+    a.pcm, a.pcm_type, a.L = base + seg["pcm"][0], _native.PCM_I16, L
+    a.r, a.r_type = base + seg["hand"][0], kinds[hand_dtype]
+    a.d, a.d_type = base + seg["depth"][0], kinds[depth_dtype]
+    a.t = base + seg["force"][0]
+    a.range_in[:] = [0, 255, 0, 255, 0, 400]        # normalised_sensors' ranges
+    how = norm_division or ("reciprocal" if device_divides_by_reciprocal(dev) else "ieee")
+    if how not in ("ieee", "reciprocal"):
+        raise ValueError(f"{who}.norm_division={how!r} ('ieee', 'reciprocal' or None)")
+    a.norm_rcp = int(how == "reciprocal")
+    a.sr, a.n_fft, a.n_mels, a.n_mfcc = fe.params
+    a.plan, a.plan_bytes = ptr(fe.plan), fe.plan.numel()
+    a.mfcc_out, a.mfcc_out_bytes = ptr(t["mfcc"]), t["mfcc"].numel() * 4
+    a.mfcc_norm, a.mfcc_norm_bytes = ptr(t["norm"]), t["norm"].numel() * 4
+    a.mfcc_ws, a.mfcc_ws_bytes = ptr(t["ws"]), t["ws"].numel()
+    a.hsr_weights, a.hsr_weight_count = ptr(t["weights"]), t["weights"].numel()
+    a.x, a.ld_x, a.B, a.rows = ptr(x), x.stride(0), B, rows
+    t["args"] = a
+    return t
+
+
+def _stage_queues(who, t, force_q, hand_q, depth_q, mic_q):
+    """The queues of one tick into the pinned staging buffer of ``t``
+    (_bind_front) with numpy, then its copy to the device on the current
+    stream: the first B frames of force, hand and depth, all of mic_q (int16
+    samples or the reference's list of ``bytes`` chunks)."""
+    B, L, v = t["B"], t["L"], t["views"]
+    if isinstance(mic_q, (bytes, bytearray, memoryview)):
+        mic_q = [mic_q]
+    chunks = isinstance(mic_q, (list, tuple)) and (not mic_q or isinstance(mic_q[0], (bytes, bytearray, memoryview)))
+    if chunks:
+        n_mic = sum(len(c) for c in mic_q) // 2
+    else:
+        mic_q = np.asarray(mic_q).reshape(-1)
+        if mic_q.dtype != np.int16:
+            raise ValueError(f"{who}.tick: PCM of dtype {mic_q.dtype} (the staging buffer holds int16)")
+        n_mic = mic_q.size
+    if n_mic != L:
+        raise ValueError(f"{who}.tick: a mic queue of {n_mic} samples, bound to {L}; score_sensors takes "
+                         "a queue that is still filling")
+    qs = {}
+    for name, q in (("force", force_q), ("hand", hand_q), ("depth", depth_q)):
+        q = np.asarray(q)
+        q = q.reshape(q.shape[0], -1) if q.ndim > 1 else q.reshape(-1, 1)
+        if q.shape[0] < B:
+            raise ValueError(f"{who}.tick: {name} queue of {q.shape[0]} frames < the {B} windows of a tick")
+        if q.shape[1] != v[name].reshape(B, -1).shape[1]:
+            raise ValueError(f"{who}.tick: {name} frames of {q.shape[1]} values")
+        if v[name].dtype == np.uint8 and q.dtype != np.uint8:
+            raise ValueError(f"{who}.tick: {name} queue of {q.dtype}, bound as uint8")
+        qs[name] = q[:B]
+    t["copied"].synchronize()            # the last tick's copy has read the staging buffer
+    if chunks:
+        np.copyto(v["pcm"], np.frombuffer(b"".join(mic_q), dtype=np.int16))
+    else:
+        np.copyto(v["pcm"], mic_q)
+    for name, q in qs.items():
+        np.copyto(v[name].reshape(B, -1), q, casting="same_kind")
+    t["raw"].copy_(t["host"], non_blocking=True)
+    t["copied"].record()
+
+
 class OnlineScorer:
     # per-modality scores: off unless ``groups`` is given (then instance attributes)
     groups = None
@@ -266,75 +396,10 @@ class OnlineScorer:
         HSR weights, packed once (``refresh_sensors`` repacks them).
         front_end: an MfccFrontEnd (None: ``self.front_end``, else the
         reference's 44.1 kHz / 0.1 s / 128 mel / 13 settings)."""
-        from . import _native
-        from .data_loaders import mic_front_end
-        B = int(hsr_net.batch_size)
-        if B > self.rows:
-            raise ValueError(f"OnlineScorer.bind_sensors: slicing_size {B} > {self.rows}; score_windows "
-                             "(reconstruction_aggregation) is the batch route")
-        if hsr_net.unimodal:
-            raise ValueError("OnlineScorer.bind_sensors: the tick fuses all four streams (a fused HSR_Net)")
-        kinds = {np.dtype(np.uint8): _native.SRC_U8, np.dtype(np.float32): _native.SRC_F32}
-        hand_dtype, depth_dtype = np.dtype(hand_dtype), np.dtype(depth_dtype)
-        if hand_dtype not in kinds or depth_dtype not in kinds:
-            raise ValueError(f"OnlineScorer.bind_sensors: hand / depth of {hand_dtype} / {depth_dtype} (uint8 or float32)")
-        dev = self.x.device
-        fe = front_end or self.front_end or mic_front_end(device=dev)
-        self.front_end = fe
-        L = int(mic_samples)
-        F = fe.frames(L)
-        if F < B:
-            raise ValueError(f"OnlineScorer.bind_sensors: {L} samples are {max(F, 0)} frames < the {B} windows of a tick")
-        if fe.n_mfcc != 13 or self.x.shape[1] != 1728:
-            raise ValueError("OnlineScorer.bind_sensors: the fused row takes 13 MFCCs and a 1728-wide model")
-        # the staging layout: name -> (byte offset, dtype, shape)
-        seg, off = {}, 0
-        for name, dt, shape in (("pcm", np.dtype(np.int16), (L,)), ("hand", hand_dtype, (B, 3072)),
-                                ("depth", depth_dtype, (B, 1024)), ("force", np.dtype(np.float32), (B,))):
-            seg[name] = (off, dt, shape)
-            off = (off + int(np.prod(shape)) * dt.itemsize + 255) // 256 * 256
-        host = torch.zeros(off, dtype=torch.uint8).pin_memory()
-        raw = torch.zeros(off, dtype=torch.uint8, device=dev)
-        flat = host.numpy()
-        views = {k: flat[o:o + int(np.prod(s)) * dt.itemsize].view(dt).reshape(s) for k, (o, dt, s) in seg.items()}
-        lib = _native.load()
-        t = dict(B=B, L=L, net=hsr_net, host=host, raw=raw, views=views, copied=torch.cuda.Event(),
-                 mfcc=torch.zeros((F, 13), device=dev), norm=torch.zeros((B, 13), device=dev),
-                 ws=torch.zeros(int(lib.mmad_mfcc_ws_bytes(F, fe.n_mels)), dtype=torch.uint8, device=dev),
-                 weights=torch.zeros(int(lib.mmad_hsr_weight_count()), device=dev))
-        hsr_net.packed_weights(out=t["weights"])
-        a, ptr = _native.TickArgs(), (lambda v: v.data_ptr())
-        base = raw.data_ptr()
-        a.pcm, a.pcm_type, a.L = base + seg["pcm"][0], _native.PCM_I16, L
-        a.r, a.r_type = base + seg["hand"][0], kinds[hand_dtype]
-        a.d, a.d_type = base + seg["depth"][0], kinds[depth_dtype]
-        a.t = base + seg["force"][0]
-        a.range_in[:] = [0, 255, 0, 255, 0, 400]        # normalised_sensors' ranges
-        how = self.norm_division or ("reciprocal" if device_divides_by_reciprocal(dev) else "ieee")
-        if how not in ("ieee", "reciprocal"):
-            raise ValueError(f"OnlineScorer.norm_division={how!r} ('ieee', 'reciprocal' or None)")
-        a.norm_rcp = int(how == "reciprocal")
-        a.sr, a.n_fft, a.n_mels, a.n_mfcc = fe.params
-        a.plan, a.plan_bytes = ptr(fe.plan), fe.plan.numel()
-        a.mfcc_out, a.mfcc_out_bytes = ptr(t["mfcc"]), t["mfcc"].numel() * 4
-        a.mfcc_norm, a.mfcc_norm_bytes = ptr(t["norm"]), t["norm"].numel() * 4
-        a.mfcc_ws, a.mfcc_ws_bytes = ptr(t["ws"]), t["ws"].numel()
-        a.hsr_weights, a.hsr_weight_count = ptr(t["weights"]), t["weights"].numel()
-        a.x, a.ld_x, a.B, a.rows = ptr(self.x), self.x.stride(0), B, self.rows
-        a.sap_start, a.sap_end = self.start, self.end
-        a.thresholds, a.out, a.flags = ptr(self.thresholds), ptr(self.out), ptr(self.flags)
-
-        def aligned(buf):
-            p = (buf.data_ptr() + 255) // 256 * 256
-            return p, buf.numel() - (p - buf.data_ptr())
-        a.state, a.state_bytes = aligned(self.state)
-        if self.groups is not None:
-            t["bounds"] = (ctypes.c_int * len(self.groups))(*self.groups)
-            a.bounds, a.G = t["bounds"], len(self.groups) - 1
-            a.group_thresholds, a.group_out = ptr(self.group_thresholds), ptr(self.group_out)
-            a.group_flags = ptr(self.group_flags)
-            a.gstate, a.gstate_bytes = aligned(self.groups_state)
-        t["args"] = a
+        t = _bind_front("OnlineScorer", self.x, self.rows, hsr_net, mic_samples, hand_dtype, depth_dtype,
+                        front_end or self.front_end, self.norm_division, fused_model=True)
+        self.front_end = t["front_end"]
+        _member_args(self, t["args"], t)
         self._tick = t
         return self
 
@@ -357,45 +422,199 @@ class OnlineScorer:
         t = self._tick
         if t is None:
             raise ValueError("OnlineScorer.tick: call bind_sensors first")
-        B, L, v = t["B"], t["L"], t["views"]
-        if isinstance(mic_q, (bytes, bytearray, memoryview)):
-            mic_q = [mic_q]
-        chunks = isinstance(mic_q, (list, tuple)) and (not mic_q or isinstance(mic_q[0], (bytes, bytearray, memoryview)))
-        if chunks:
-            n_mic = sum(len(c) for c in mic_q) // 2
-        else:
-            mic_q = np.asarray(mic_q).reshape(-1)
-            if mic_q.dtype != np.int16:
-                raise ValueError(f"OnlineScorer.tick: PCM of dtype {mic_q.dtype} (the staging buffer holds int16)")
-            n_mic = mic_q.size
-        if n_mic != L:
-            raise ValueError(f"OnlineScorer.tick: a mic queue of {n_mic} samples, bound to {L}; score_sensors takes "
-                             "a queue that is still filling")
-        qs = {}
-        for name, q in (("force", force_q), ("hand", hand_q), ("depth", depth_q)):
-            q = np.asarray(q)
-            q = q.reshape(q.shape[0], -1) if q.ndim > 1 else q.reshape(-1, 1)
-            if q.shape[0] < B:
-                raise ValueError(f"OnlineScorer.tick: {name} queue of {q.shape[0]} frames < the {B} windows of a tick")
-            if q.shape[1] != v[name].reshape(B, -1).shape[1]:
-                raise ValueError(f"OnlineScorer.tick: {name} frames of {q.shape[1]} values")
-            if v[name].dtype == np.uint8 and q.dtype != np.uint8:
-                raise ValueError(f"OnlineScorer.tick: {name} queue of {q.dtype}, bound as uint8")
-            qs[name] = q[:B]
-        t["copied"].synchronize()            # the last tick's copy has read the staging buffer
-        if chunks:
-            np.copyto(v["pcm"], np.frombuffer(b"".join(mic_q), dtype=np.int16))
-        else:
-            np.copyto(v["pcm"], mic_q)
-        for name, q in qs.items():
-            np.copyto(v[name].reshape(B, -1), q, casting="same_kind")
-        t["raw"].copy_(t["host"], non_blocking=True)
-        t["copied"].record()
+        _stage_queues("OnlineScorer", t, force_q, hand_q, depth_q, mic_q)
         self.nat.online_tick(t["args"])
-        return self._results(B)
+        return self._results(t["B"])
 
     def close(self):
         """Detach the fit from the model."""
         if self.nap is not None:
             self.nap.detach()
             self.nap = None
+
+
+# config.sensor names -> the modality keys of HSR_Net.modality_columns()
+SENSOR_KEYS = {"All": None, "hand_camera": "r", "head_depth": "d", "force_torque": "t", "mic": "m"}
+
+
+class SensorBank:
+    """Several OnlineScorers -- the fused detector and its unimodal siblings,
+    independent models -- scored on ONE shared input row per tick, sharing
+    launches (mmad_online_bank_score / _tick; DESIGN.md §4 "Sensor bank"):
+    layer step l of every member is one grouped launch, the whole bank one
+    replayed graph.  Each scorer keeps its own state, outputs, thresholds, fit
+    and groups (``calibrate`` stays per scorer), and every scoring method
+    returns {name: what that scorer's own call returns} -- views of the
+    scorers' fixed outputs, bit for bit what the scorer alone computes on its
+    columns.
+
+    The bank shares one fused HSR_Net (``score_frames`` / ``score_sensors`` /
+    ``tick``): there are no per-member HSR weights, so the unimodal models are
+    expected to have been trained on that network's blocks of the fused row."""
+
+    norm_division = None     # as OnlineScorer.norm_division
+    front_end = None
+    _tick = None
+    _h = None
+
+    def __init__(self, scorers, columns=None, width=None):
+        """scorers: a mapping name -> OnlineScorer or a sequence (named by
+        position), 1..8 of them, of one row capacity and on one device.
+        columns: the first column of the shared row each scorer reads (a
+        mapping by name or a sequence; None: every scorer reads column 0);
+        scorer i reads [c, c + D_i).  The native pack reads 16-byte quads, so a
+        column start must be a multiple of 4.  width: the shared row's width
+        (None: where the last member's columns end)."""
+        from . import _native
+        items = list(scorers.items()) if hasattr(scorers, "items") else list(enumerate(scorers))
+        if not 1 <= len(items) <= _native.MAX_BANK:
+            raise ValueError(f"SensorBank: {len(items)} scorers (1..{_native.MAX_BANK})")
+        self.names = tuple(n for n, _ in items)
+        self.scorers = {n: s for n, s in items}
+        members = [s for _, s in items]
+        if len({s.rows for s in members}) != 1:
+            raise ValueError(f"SensorBank: scorers of mixed rows {[s.rows for s in members]}; one row capacity a bank")
+        if len({s.x.device for s in members}) != 1:
+            raise ValueError("SensorBank: scorers on different devices")
+        self.rows = members[0].rows
+        if columns is None:
+            cols = [0] * len(members)
+        elif hasattr(columns, "items"):
+            cols = [int(columns[n]) for n in self.names]
+        else:
+            cols = [int(c) for c in columns]
+        if len(cols) != len(members) or min(cols) < 0:
+            raise ValueError("SensorBank: one non-negative column start per scorer")
+        self.columns = {n: (c, c + s.x.shape[1]) for n, c, s in zip(self.names, cols, members)}
+        dev = members[0].x.device
+        self.x = torch.zeros((self.rows, max([int(width or 0)] + [c1 for _, c1 in self.columns.values()])),
+                             device=dev)
+        lib = _native.load()
+        n = len(members)
+        self._handles = (ctypes.c_void_p * n)(*[s.nat._h for s in members])
+        self._col0 = (ctypes.c_int * n)(*cols)
+        h = ctypes.c_void_p()
+        _native.check(lib.mmad_online_bank_create(ctypes.byref(h), n, self._handles, self._col0, self.rows),
+                      "mmad_online_bank_create")
+        self._h, self._lib = h, lib
+        self._keep = [dict() for _ in members]
+        self._members = (_native.BankMember * n)()
+        for sc, m, keep in zip(members, self._members, self._keep):
+            _member_args(sc, m, keep)
+
+    @classmethod
+    def for_sensors(cls, hsr_net, scorers):
+        """scorers: config.sensor name ('All', 'hand_camera', 'head_depth',
+        'force_torque', 'mic') -> OnlineScorer; the column starts are those of
+        ``hsr_net.modality_columns()`` (a fused HSR_Net), 'All' at 0."""
+        cols = hsr_net.modality_columns()
+        starts = {}
+        for name in scorers:
+            if name not in SENSOR_KEYS:
+                raise ValueError(f"SensorBank.for_sensors: unknown sensor {name!r} ({', '.join(SENSOR_KEYS)})")
+            key = SENSOR_KEYS[name]
+            starts[name] = 0 if key is None else cols[key][0]
+        return cls(scorers, starts, width=max(c1 for _, c1 in cols.values()))
+
+    def graph_nodes(self):
+        """Kernel nodes of the last captured pass (mmad_online_bank_graph_nodes)."""
+        return int(self._lib.mmad_online_bank_graph_nodes(self._h))
+
+    def graph_count(self):
+        return int(self._lib.mmad_online_bank_graph_count(self._h))
+
+    def _results(self, B):
+        return {n: s._results(B) for n, s in self.scorers.items()}
+
+    def _run(self, B, graph=True):
+        from . import _native
+        for s in self.scorers.values():
+            s.nat.sync_shadow()
+        _native.check(self._lib.mmad_online_bank_score(self._h, self.x.data_ptr(), self.x.stride(0), int(B),
+                                                       self._members, 1 if graph else 0, _native.stream_ptr()),
+                      "mmad_online_bank_score")
+        return self._results(B)
+
+    def score(self, x):
+        """x: [B <= rows, W] (W the bank's row width, ``self.x.shape[1]``),
+        host or device.  Returns {name: OnlineScorer.score's dict for
+        x[:, c0:c1]}."""
+        x = torch.as_tensor(x)
+        x = x.reshape(x.shape[0], -1)
+        B = x.shape[0]
+        if B > self.rows:
+            raise ValueError(f"SensorBank.score: {B} windows > {self.rows}; score_windows "
+                             "(reconstruction_aggregation) is the batch route")
+        if B < 1 or x.shape[1] != self.x.shape[1]:
+            raise ValueError(f"SensorBank.score: x must be [1..{self.rows}, {self.x.shape[1]}], got {tuple(x.shape)}")
+        self.x[:B].copy_(x, non_blocking=True)
+        return self._run(B)
+
+    def score_frames(self, hsr_net, r, d, t, m):
+        """OnlineScorer.score_frames for the bank: HSR_Net.forward of the
+        latest frames into the shared row, then the bank's pass."""
+        B = int(hsr_net.batch_size)
+        if B > self.rows:
+            raise ValueError(f"SensorBank.score_frames: slicing_size {B} > {self.rows}; score_windows "
+                             "(reconstruction_aggregation) is the batch route")
+        if hsr_net.unimodal or self.x.shape[1] != 1728:
+            raise ValueError("SensorBank.score_frames: a fused HSR_Net and a 1728-wide shared row")
+        hsr_net.forward(r, d, None, t, m, out=self.x)
+        return self._run(B)
+
+    def score_sensors(self, hsr_net, force_q, hand_q, depth_q, mic_pcm):
+        """OnlineScorer.score_sensors for the bank (a microphone queue that
+        is still filling; ``tick`` is the one-graph route)."""
+        from .data_loaders import mic_front_end, normalised_sensors
+        dev = self.x.device
+        if self.front_end is None:
+            self.front_end = mic_front_end(device=dev)
+        r, d, t = normalised_sensors(force_q, hand_q, depth_q, dev)
+        m = self.front_end.latest(mic_pcm, int(hsr_net.batch_size))[1]
+        return self.score_frames(hsr_net, r, d, t, m)
+
+    def bind_sensors(self, hsr_net, mic_samples, hand_dtype=np.uint8, depth_dtype=np.uint8, front_end=None):
+        """OnlineScorer.bind_sensors for the bank: the same staging buffer,
+        MFCC buffers and packed weights, one set for all members; the fused
+        row lands in the bank's shared ``x`` (1728 wide at least).  The bank
+        needs no fused member: a bank of one 'mic' scorer is the unimodal tick."""
+        t = _bind_front("SensorBank", self.x, self.rows, hsr_net, mic_samples, hand_dtype, depth_dtype,
+                        front_end or self.front_end, self.norm_division)
+        self.front_end = t["front_end"]
+        self._tick = t
+        return self
+
+    def refresh_sensors(self):
+        """Repack the bound HSR_Net's weights into the buffer the bank's graph
+        reads: the next ``tick`` sees them, no new capture."""
+        if self._tick is None:
+            raise ValueError("SensorBank.refresh_sensors: call bind_sensors first")
+        self._tick["net"].packed_weights(out=self._tick["weights"])
+
+    def tick(self, force_q, hand_q, depth_q, mic_q):
+        """One sensor tick for every member: one host-to-device copy and one
+        graph launch (mmad_online_bank_tick: MFCC -> fusion -> the bank's
+        pass).  Returns {name: what that scorer's ``tick`` returns}."""
+        from . import _native
+        t = self._tick
+        if t is None:
+            raise ValueError("SensorBank.tick: call bind_sensors first")
+        _stage_queues("SensorBank", t, force_q, hand_q, depth_q, mic_q)
+        for s in self.scorers.values():
+            s.nat.sync_shadow()
+        _native.check(self._lib.mmad_online_bank_tick(self._h, ctypes.byref(t["args"]), self._members, 1,
+                                                      _native.stream_ptr()), "mmad_online_bank_tick")
+        return self._results(t["B"])
+
+    def close(self):
+        """Drop the bank's captured graphs and native object (the scorers,
+        their fits included, stay as they are: close them on their own)."""
+        if self._h is not None:
+            self._lib.mmad_online_bank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -237,6 +237,36 @@ int mmad_fc_rows64(int dtype, int M, int N, int K, int Np, int Kp, const void* x
                    const float* bn_shift, void* y, const void* ref, int ref_dtype, int ldref,
                    float* diff, int lddiff, const float* colw, float* rowsq, void* stream);
 
+/* The same operator for up to MMAD_MAX_BANK independent members in one launch
+ * per element type (the sensor bank's layer step, mmad_online_bank_score): a
+ * descriptor holds the arguments of mmad_fc_rows16 / mmad_fc_rows64, dtype
+ * included; `rows` (16 or 64) is shared, M may differ.  A block finds its
+ * (member, 16-column tile) in a prefix table of per-member tile counts passed
+ * by value in the kernel arguments; no atomics, no grid-wide wait, no flag in
+ * memory, no cooperative launch.  Members of MMAD_F32 and of MMAD_BF16 in one
+ * call are two launches.  Every member's y, diff and rowsq -- the zeroed rows
+ * >= M and columns >= N included -- equal, bit for bit, what mmad_fc_rows16 /
+ * mmad_fc_rows64 write for that member alone (the same per-tile body and K
+ * order; all members ride ceil(max M / 16) row tiles, and a row tile past a
+ * member's own M reads zero rows of x and writes the zeros the single form
+ * writes).  A descriptor with N == 0 is an empty member: it owns no blocks and
+ * none of its other fields is read.  d: a HOST array.
+ * MMAD_EINVAL, nothing launched: n outside 1..MMAD_MAX_BANK, rows other than
+ * 16 / 64, a null d, any non-empty member that mmad_fc_rows16 / mmad_fc_rows64
+ * refuses (MMAD_EUNSUPPORTED where they return it). */
+#define MMAD_MAX_BANK 8
+typedef struct mmad_fc_rows_desc {
+  int dtype, M, N, K, Np, Kp;
+  const void* x; const void* w; const float* bias;
+  int act; float slope;
+  const float* bn_scale; const float* bn_shift;
+  void* y;
+  const void* ref; int ref_dtype, ldref;
+  float* diff; int lddiff;
+  const float* colw; float* rowsq;
+} mmad_fc_rows_desc;
+int mmad_fc_rows_group(int rows, int n, const mmad_fc_rows_desc* d, void* stream);
+
 /* Mean square of column groups of an fp32 matrix: the per-modality anomaly
  * scores (no reference counterpart).  bounds: HOST array of G + 1 strictly
  * ascending columns, 0 <= bounds[0], bounds[G] <= ldd, 1 <= G <=
@@ -1096,6 +1126,74 @@ typedef struct mmad_tick_args {
   void* gstate; int64_t gstate_bytes;
 } mmad_tick_args;
 int mmad_ae_online_tick(mmad_ae* h, const mmad_tick_args* a, int use_graph, void* stream);
+
+/* Sensor bank: the online pass of up to MMAD_MAX_BANK independent models (the
+ * fused detector and its unimodal siblings: separate handles, not the column
+ * groups of one model) on ONE shared input, sharing launches.  The pass walks
+ * the steps of the single pass once -- pack, BN fold, pass 1 layer by layer,
+ * pass 2 layer by layer, NAP, finish -- and issues one grouped launch per
+ * step over the members that have that step (mmad_fc_rows_group and the
+ * grouped pack / fold / finish kernels; a layer step is two launches when its
+ * members are of both element types; the VIB reparameterisation and
+ * mmad_group_sq stay one launch per member that uses them).  Members may
+ * differ in depth, width, dtype, VIB, attached fit and groups.  Every member's
+ * out, flags, group_out and group_flags are, bit for bit, what its own
+ * mmad_ae_online_score / _score64 / _score_groups call writes given
+ * x + col0[i] with the same ld_x.
+ * create: handles[i] (not owned; they outlive the bank) reads the columns
+ * [col0[i], col0[i] + D_i) of the shared x; rows (16 / 64) is every member's
+ * row capacity.  mmad_online_bank_state_bytes(bank, i) is member i's
+ * mmad_ae_online_state_bytes (rows 16) or _bytes64 (rows 64): a member's state
+ * (and gstate) may be the very buffers its own calls use, bank and single
+ * calls taking turns.
+ * members[i]: the per-member arguments of mmad_ae_online_score_groups (bounds
+ * == NULL: an ungrouped member), as a HOST array of the bank's n entries.
+ * The grouped pack kernel reads x with 16-byte loads: x + col0[i] must be
+ * 16-byte aligned and ld_x a multiple of 4.
+ * use_graph != 0: the first call for a signature (every member's own
+ * signature, on the shared x) runs eagerly and captures one linear chain on
+ * one stream -- no parallel branches, no second stream; later calls are one
+ * hipGraphLaunch.  The bank owns up to 8 captured passes
+ * (mmad_online_bank_graph_count; mmad_online_bank_destroy drops them) and
+ * every buffer is read at replay time, as for the handle's online graphs.
+ * Re-attaching a fit to a member makes a new signature only if the fit's
+ * buffers moved: destroy and re-create the bank after changing a member's
+ * fit.  mmad_online_bank_graph_nodes: the kernel-node count of the last
+ * captured pass (0 before the first capture).
+ * mmad_online_bank_tick is mmad_ae_online_tick with the bank pass in place of
+ * the single pass: of `a` it reads the raw queues, the front end, the fusion
+ * producer and x, ld_x, B, rows; the single pass's fields (sap_start ..
+ * gstate_bytes) are ignored in favour of members[].  The fused row (ld_x >=
+ * 1728) is required of x, not of any member: a bank may hold no fused member
+ * (a bank of one `mic` model is the unimodal tick).  All members read the one
+ * fused row, i.e. one set of HSR weights.
+ * MMAD_EINVAL, nothing launched and nothing captured: n outside
+ * 1..MMAD_MAX_BANK, rows other than 16 / 64 (create; tick: a->rows other than
+ * the bank's), a null handle, col0[i] < 0, more than 64 BatchNorm layers over
+ * all members; col0[i] + D_i > ld_x, a misaligned x + col0[i] or ld_x, and
+ * every refusal of the member's own online entry point (and, for the tick, of
+ * mmad_mfcc and mmad_hsr_fuse_raw).
+ * These entries are additive: MMAD_ABI_VERSION stays 1 and covers them from
+ * this header on (the struct layouts below included). */
+typedef struct mmad_online_bank mmad_online_bank;
+typedef struct mmad_bank_member {
+  int sap_start, sap_end;
+  const float* thresholds; float* out; uint8_t* flags;
+  void* state; int64_t state_bytes;
+  const int* bounds; int G;
+  const float* group_thresholds; float* group_out; uint8_t* group_flags;
+  void* gstate; int64_t gstate_bytes;
+} mmad_bank_member;
+int mmad_online_bank_create(mmad_online_bank** bank, int n, mmad_ae* const* handles, const int* col0,
+                            int rows);
+void mmad_online_bank_destroy(mmad_online_bank* bank);
+int64_t mmad_online_bank_state_bytes(const mmad_online_bank* bank, int i);
+int mmad_online_bank_score(mmad_online_bank* bank, const float* x, int ld_x, int B,
+                           const mmad_bank_member* members, int use_graph, void* stream);
+int mmad_online_bank_tick(mmad_online_bank* bank, const mmad_tick_args* a,
+                          const mmad_bank_member* members, int use_graph, void* stream);
+int mmad_online_bank_graph_nodes(const mmad_online_bank* bank);
+int mmad_online_bank_graph_count(const mmad_online_bank* bank);
 
 #ifdef __cplusplus
 }

@@ -41,7 +41,16 @@ once (AE weights + the encoder again + V^T) / 8 TB/s.
       scorer and the same raw queues, alternated call by call in one process:
       10 windows on 16 rows and 32 windows on 64 rows, the 1728-wide 3-layer
       fp32 model with the modality groups.  The baseline is the score_sensors
-      of the same run; a GPU-time ratio inside 1 +- 3 % is no gain."""
+      of the same run; a GPU-time ratio inside 1 +- 3 % is no gain.
+  python tools/online_latency.py --bank [--out profiles/online_bank_latency.json]
+      the sensor bank (SensorBank.tick: one copy and one replay of
+      mmad_online_bank_tick for all members) against the members' own calls one
+      after another (the fused scorer's tick, then each unimodal scorer's score
+      on its columns of the fused row), and a one-member bank against
+      OnlineScorer.tick; 10 windows on 16 rows and 32 windows on 64 rows; five
+      fp32 members of D = 1728 / 1024 / 512 / 64 / 128, btl 100, 5 layers, a
+      full-range fp32 fit on the fused one.  Pairs alternate call by call in one
+      process; a GPU-time ratio inside 1 +- 3 % decides nothing."""
 import argparse
 import ctypes
 import json
@@ -320,6 +329,107 @@ def run_tick(B, rows):
     return res
 
 
+BANK_WIDTHS = {"All": 1728, "hand_camera": 1024, "head_depth": 512, "force_torque": 64, "mic": 128}
+
+
+def bank_members(rows, names):
+    """name -> OnlineScorer over a btl-100, 5-layer fp32 model of that sensor's
+    width (a full-range fp32 fit with random values on the fused member)."""
+    from icra2021_multimodal_ad_amd.model_builder import get_model
+    from icra2021_multimodal_ad_amd.online import OnlineScorer
+    out = {}
+    for i, name in enumerate(names):
+        torch.manual_seed(20 + i)
+        m = get_model(types.SimpleNamespace(input_size=BANK_WIDTHS[name], btl_size=100, n_layers=5, gpu_id=0,
+                                            dtype="f32", models="ae"))
+        m.eval()
+        if name == "All":
+            fit = random_fit(m._native)
+            m._native.set_nap(fit)
+            m._fit = fit                     # the handle reads these buffers: keep them alive
+        out[name] = OnlineScorer(m, rows=rows)
+    return out
+
+
+def run_bank(B, rows):
+    """SensorBank.tick against the members' own calls one after another (what
+    the deployment loop had to do before the bank: the fused scorer's tick,
+    then every unimodal scorer's ``score`` on its columns of the fused row the
+    tick left on the device), and a one-member bank against OnlineScorer.tick.
+    Each pair alternates call by call in one process; the two sides of a pair
+    run on their own model copies (the same seeds), so neither re-zeroes the
+    other's NAP operand."""
+    from icra2021_multimodal_ad_amd.hsr_net import HSR_Net
+    from icra2021_multimodal_ad_amd.online import SensorBank
+    torch.manual_seed(7)
+    net = HSR_Net(False, types.SimpleNamespace(slicing_size=B, batch_size=B, gpu_id=0)).cuda()
+    rng = np.random.Generator(np.random.PCG64(81))
+    hand_q = rng.integers(0, 256, size=(B, 32 * 32 * 3)).astype(np.uint8)
+    depth_q = rng.integers(0, 256, size=(B, 32 * 32)).astype(np.uint8)
+    force_q = rng.uniform(0, 400, size=B)
+    pcm = rng.integers(-8000, 8000, size=(B + 1) * 4410 - 2205).astype(np.int16)   # B + 1 frames
+    q = (force_q, hand_q, depth_q, pcm)
+    keep = lambda r: {k: v.clone() for k, v in r.items() if v is not None}   # noqa: E731
+    names = tuple(BANK_WIDTHS)
+    res = {"B": B, "rows": rows, "pcm_samples": len(pcm)}
+
+    # ---- five members: the bank against the members in sequence
+    bank = SensorBank.for_sensors(net, bank_members(rows, names)).bind_sensors(net, len(pcm))
+    seq = bank_members(rows, names)
+    seq["All"].bind_sensors(net, len(pcm))
+    cols = bank.columns
+
+    def sequence():
+        out = {"All": seq["All"].tick(*q)}
+        row = seq["All"].x
+        for n in names[1:]:
+            c0, c1 = cols[n]
+            out[n] = seq[n].score(row[:B, c0:c1])
+        return out
+    a, b = bank.tick(*q), sequence()
+    res["five_members_bits_equal"] = all(torch.equal(a[n][k], b[n][k]) for n in names for k in keep(a[n]))
+    m5 = measure({"members_in_sequence": sequence, "bank_tick": lambda: bank.tick(*q)})
+    res["five_members"] = m5
+    res["five_members"]["graph_nodes"] = bank.graph_nodes()
+    # ---- one member: the bank against OnlineScorer.tick
+    bank1 = SensorBank.for_sensors(net, bank_members(rows, ("All",))).bind_sensors(net, len(pcm))
+    single = bank_members(rows, ("All",))["All"].bind_sensors(net, len(pcm))
+    a, b = keep(bank1.tick(*q)["All"]), keep(single.tick(*q))
+    res["one_member_bits_equal"] = all(torch.equal(a[k], b[k]) for k in a)
+    m1 = measure({"scorer_tick": lambda: single.tick(*q), "bank_tick": lambda: bank1.tick(*q)})
+    res["one_member"] = m1
+    res["one_member"]["graph_nodes"] = bank1.graph_nodes()
+    for kind in ("gpu", "wall"):
+        res[f"bank5_vs_sequence_{kind}"] = (m5["bank_tick"][kind]["median_us"]
+                                            / m5["members_in_sequence"][kind]["median_us"])
+        res[f"bank1_vs_scorer_tick_{kind}"] = m1["bank_tick"][kind]["median_us"] / m1["scorer_tick"][kind]["median_us"]
+    print(f"bank B={B} rows={rows}",
+          {k: (round(v["gpu"]["median_us"], 1), round(v["wall"]["median_us"], 1)) for k, v in m5.items()
+           if isinstance(v, dict)},
+          {k: (round(v["gpu"]["median_us"], 1), round(v["wall"]["median_us"], 1)) for k, v in m1.items()
+           if isinstance(v, dict)},
+          f"bits equal: {res['five_members_bits_equal']} {res['one_member_bits_equal']}", flush=True)
+    bank.close()
+    bank1.close()
+    return res
+
+
+def main_bank(out):
+    cases = {f"f32_B{B}_rows{rows}": run_bank(B, rows) for B, rows in TICK_CASES}
+    doc = {"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "calls": CALLS, "spread": SPREAD,
+           "members": {n: f"input {d}, btl 100, 5 layers, fp32" + (", full-range fp32 fit" if n == "All" else "")
+                       for n, d in BANK_WIDTHS.items()},
+           "cases": cases,
+           "bank5_faster_than_sequence_outside_spread": {k: c["bank5_vs_sequence_gpu"] for k, c in cases.items()
+                                                         if c["bank5_vs_sequence_gpu"] < 1 - SPREAD},
+           "bank1_slower_than_scorer_tick_outside_spread": {k: c["bank1_vs_scorer_tick_gpu"]
+                                                            for k, c in cases.items()
+                                                            if c["bank1_vs_scorer_tick_gpu"] > 1 + SPREAD}}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+
+
 def main_tick(out):
     cases = {f"f32_B{B}_rows{rows}": run_tick(B, rows) for B, rows in TICK_CASES}
     doc = {"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "calls": CALLS, "spread": SPREAD,
@@ -372,8 +482,11 @@ def main():
     ap.add_argument("--rows64", action="store_true")
     ap.add_argument("--groups", action="store_true")
     ap.add_argument("--tick", action="store_true")
+    ap.add_argument("--bank", action="store_true")
     a = ap.parse_args()
     _native.require_gpu()
+    if a.bank:
+        return main_bank(a.out or "profiles/online_bank_latency.json")
     if a.tick:
         return main_tick(a.out or "profiles/online_tick_latency.json")
     if a.rows64:
