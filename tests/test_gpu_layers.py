@@ -216,13 +216,9 @@ def test_public_adam_matches_torch_cpu_adam(betas, step, lr):
     m0 = torch.randn(n, generator=g_) * 1e-3 if step > 1 else torch.zeros(n)
     v0 = torch.rand(n, generator=g_) * 1e-5 if step > 1 else torch.zeros(n)
     # torch CPU, foreach=False (_single_tensor_adam), state after step - 1 steps
-    prm = torch.nn.Parameter(p0.clone())
-    opt = torch.optim.Adam([prm], lr=lr, betas=betas, eps=1e-8, foreach=False)
-    opt.state[prm] = {"step": torch.tensor(float(step - 1)), "exp_avg": m0.clone(),
-                      "exp_avg_sq": v0.clone()}
-    prm.grad = g.clone()
-    opt.step()
-    st = opt.state[prm]
+    from tests.adam_ref import torch_cpu_adam
+    prm, exp_avg, exp_avg_sq = torch_cpu_adam(p0, g, m0, v0, lr=lr, betas=betas, eps=1e-8, step=step)
+    st = {"exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
     # the product: step size / bias correction as the executor forms them
     b1, b2 = betas
     step_size = lr / (1.0 - b1 ** step)
