@@ -504,5 +504,23 @@ inline int capture_error(const GraphCaptureResult& r) {
   MMAD_HIP_CHECK(r.err);
   return MMAD_OK;
 }
+// ... and the one replay routine of the score and online paths: a hit launches
+// the cached graph on the caller's stream; a miss runs the pass there eagerly
+// (that also settles every GEMM tile choice, which cannot be timed under
+// capture), captures the same launches with capture(pass, &exec) -- capture_graph
+// or capture_graph_on, on the owner's capture stream -- and keeps the graph for
+// the next calls.  Nothing is inserted unless every stage succeeded
+template <class Key, class Capture, class Pass>
+int replay_or_capture(GraphCache<Key>& cache, const Key& key, hipStream_t st, Capture capture, Pass pass) {
+  if (hipGraphExec_t hit = cache.find(key)) {
+    MMAD_HIP_CHECK(hipGraphLaunch(hit, st));
+    return MMAD_OK;
+  }
+  RET_IF(pass(st));
+  hipGraphExec_t exec = nullptr;
+  RET_IF(capture_error(capture(pass, &exec)));
+  cache.insert(key, exec);   // bounded cache: drops the oldest pass
+  return MMAD_OK;
+}
 
 }  // namespace mmad_ae_impl

@@ -271,18 +271,8 @@ static int score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int bat
   };
   if (!use_graph) return pass(st);
   const ScoreKey key{x, ld_x, N, batch, layer_sq, ld_sq, ws, score_weights(h), nap, nap_vt};
-  if (hipGraphExec_t hit = h->graphs.find(key)) {
-    MMAD_HIP_CHECK(hipGraphLaunch(hit, st));
-    return MMAD_OK;
-  }
-  // first pass of this shape: run it eagerly (that also settles every GEMM
-  // tile choice, which cannot be timed under capture), then capture the same
-  // launches on the handle's capture stream for the next calls
-  RET_IF(pass(st));
-  hipGraphExec_t exec = nullptr;
-  RET_IF(capture_error(capture_graph(h, pass, &exec)));
-  h->graphs.insert(key, exec);   // bounded cache: drops the oldest pass
-  return MMAD_OK;
+  return replay_or_capture(h->graphs, key, st,
+                           [&](auto& p, hipGraphExec_t* exec) { return capture_graph(h, p, exec); }, pass);
 }
 
 int mmad_ae_score_stream(mmad_ae* h, const float* x, int ld_x, int64_t N, int batch,

@@ -38,6 +38,8 @@
 //     both operands' quads: k = 4 (l >> 4) + j of the 16-k step -- the same
 //     products as the natural order, summed in another, fixed order.
 //   C/D (both): column l & 15, rows 4 (l >> 4) + reg.
+#include <type_traits>
+
 #include "mmad_common.h"
 #include "mmad_ops.h"
 
@@ -310,19 +312,26 @@ __global__ __launch_bounds__(512) void online_finish_group_k(const FinishGroup g
   online_finish_body<ROWS>(g.f[blockIdx.x]);
 }
 
+// the one choice of instantiation, for both kernel families: f(RT, ROWS) as
+// integral constants, RT = the row tiles the M valid rows take (M <= rows: a
+// 16-row call only ever takes RT = 1)
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F>
+void with_tiles(int rows, int M, F f) {
+  if (rows == 16) return f(Int<1>{}, Int<16>{});
+  switch ((M + 15) / 16) {
+    case 1: return f(Int<1>{}, Int<64>{});
+    case 2: return f(Int<2>{}, Int<64>{});
+    case 3: return f(Int<3>{}, Int<64>{});
+    default: return f(Int<4>{}, Int<64>{});
+  }
+}
+
 template <typename T>
 void launch(const MmadSkinny& a, hipStream_t s) {
-  const dim3 grid(a.Np / 16), block(NW * 64);
-  if (a.rows == 16) {   // M <= rows: a 16-row call only ever takes RT = 1
-    skinny_k<T, 1, 16><<<grid, block, 0, s>>>(a);
-    return;
-  }
-  switch ((a.M + 15) / 16) {
-    case 1: skinny_k<T, 1, 64><<<grid, block, 0, s>>>(a); break;
-    case 2: skinny_k<T, 2, 64><<<grid, block, 0, s>>>(a); break;
-    case 3: skinny_k<T, 3, 64><<<grid, block, 0, s>>>(a); break;
-    default: skinny_k<T, 4, 64><<<grid, block, 0, s>>>(a); break;
-  }
+  with_tiles(a.rows, a.M, [&](auto rt, auto rows) {
+    skinny_k<T, decltype(rt)::value, decltype(rows)::value><<<dim3(a.Np / 16), dim3(NW * 64), 0, s>>>(a);
+  });
 }
 
 // the members of element type T (mask bit i) as one launch, all on RT row tiles
@@ -338,17 +347,9 @@ void launch_group(int rows, int n, unsigned mask, const MmadSkinny* a, hipStream
     maxM = a[i].M > maxM ? a[i].M : maxM;
   }
   g.n = n;
-  const dim3 grid(g.first[n]), block(NW * 64);
-  if (rows == 16) {
-    skinny_group_k<T, 1, 16><<<grid, block, 0, s>>>(g);
-    return;
-  }
-  switch ((maxM + 15) / 16) {
-    case 1: skinny_group_k<T, 1, 64><<<grid, block, 0, s>>>(g); break;
-    case 2: skinny_group_k<T, 2, 64><<<grid, block, 0, s>>>(g); break;
-    case 3: skinny_group_k<T, 3, 64><<<grid, block, 0, s>>>(g); break;
-    default: skinny_group_k<T, 4, 64><<<grid, block, 0, s>>>(g); break;
-  }
+  with_tiles(rows, maxM, [&](auto rt, auto rw) {
+    skinny_group_k<T, decltype(rt)::value, decltype(rw)::value><<<dim3(g.first[n]), dim3(NW * 64), 0, s>>>(g);
+  });
 }
 
 // every refusal of the operator, nothing launched

@@ -83,7 +83,9 @@ class NativeAE:
         self.grads = torch.zeros(self.n_params, **kw)
         self.exp_avg = torch.zeros(self.n_params, **kw)
         self.exp_avg_sq = torch.zeros(self.n_params, **kw)
-        self.running = torch.zeros(2 * self.n_bn, **kw)
+        # (one element for a model without BatchNorm -- a one-layer encoder and
+        # decoder: the native handle takes a null running pointer for unbound)
+        self.running = torch.zeros(max(2 * self.n_bn, 1), **kw)
         self.running[self.n_bn:] = 1.0
         # bf16: two weight shadows (mmad_ae_set_shadow_pair), ping-ponged by
         # the fused step on large calls (the executor picks per call: knob

@@ -223,11 +223,126 @@ def _stage_queues(who, t, force_q, hand_q, depth_q, mic_q):
     t["copied"].record()
 
 
-class OnlineScorer:
+class _SharedRoutes:
+    """The routes OnlineScorer and SensorBank share, on the fixed input row
+    ``self.x`` [rows, W]: ``score``, ``score_frames``, ``score_sensors``,
+    ``refresh_sensors`` and ``tick``.  Each class supplies ``_run(B)`` (its
+    native pass on the first B rows of ``self.x``), ``_tick_native(args)`` (its
+    native tick), ``_results(B)`` and ``_fuse`` (HSR_Net.forward into ``self.x``
+    with the class's own refusals).  Messages carry the calling class's name."""
+    front_end = None     # score_sensors' MfccFrontEnd (set one to change its settings)
+    _tick = None         # bind_sensors' buffers and argument struct
+    # norm_vec's quotient inside the tick, read by bind_sensors: 'ieee' (a
+    # correctly rounded division, mmad_hsr_fuse_raw's), 'reciprocal' (the
+    # product with fl(1 / (hi - lo))), or None: whichever of the two torch's
+    # elementwise kernels compute on the scorer's device, so that ``tick``
+    # returns score_sensors' bits (device_divides_by_reciprocal)
+    norm_division = None
+    _fused_model = False  # the tick's fused row is this object's model input (x exactly 1728 wide)
+
+    def score(self, x):
+        """x: [B <= rows, W] (W = ``self.x.shape[1]``: the model's input size,
+        or the bank's row width), host or device.  OnlineScorer returns
+        {'base','sap','nap','layer_sq','flags'}: views of its fixed outputs on
+        the device, rewritten by the next call (copy what you keep); with
+        groups also 'groups' [G, B] and 'group_flags' [G, B], rows in the order
+        of ``group_names`` (ascending columns).  SensorBank returns {name:
+        that scorer's dict for x[:, c0:c1]}."""
+        who = type(self).__name__
+        x = torch.as_tensor(x)
+        x = x.reshape(x.shape[0], -1)
+        B = x.shape[0]
+        if B > self.rows:
+            raise ValueError(f"{who}.score: {B} windows > {self.rows}; score_windows "
+                             "(reconstruction_aggregation) is the batch route")
+        if B < 1 or x.shape[1] != self.x.shape[1]:
+            raise ValueError(f"{who}.score: x must be [1..{self.rows}, {self.x.shape[1]}], got {tuple(x.shape)}")
+        self.x[:B].copy_(x, non_blocking=True)
+        return self._run(B)
+
+    def score_frames(self, hsr_net, r, d, t, m):
+        """One step of get_realtime_dataloader: HSR_Net.forward (mmad_hsr_fuse)
+        of the latest ``hsr_net.batch_size`` <= rows frames straight into the
+        fixed input row, on the same stream, then ``score``'s pass."""
+        B = int(hsr_net.batch_size)
+        if B > self.rows:
+            raise ValueError(f"{type(self).__name__}.score_frames: slicing_size {B} > {self.rows}; score_windows "
+                             "(reconstruction_aggregation) is the batch route")
+        self._fuse(hsr_net, (r, d, None, t, m), B)
+        return self._run(B)
+
+    def score_sensors(self, hsr_net, force_q, hand_q, depth_q, mic_pcm):
+        """One tick of the deployment loop from the raw queues
+        (get_realtime_dataloader, utils/data_loaders.py:734-737): norm_vec's
+        fixed-range maps of the camera, depth and force/torque frames
+        (elementwise torch), the microphone's MFCCs and their norm_vec to
+        [-1, 1] over the last ``hsr_net.batch_size`` frames (mmad_mfcc, on the
+        same stream, ahead of the replayed graph), then ``score_frames``.
+        mic_pcm: what MfccFrontEnd takes (``self.front_end``: built on first
+        use with the reference's 44.1 kHz / 0.1 s / 128 mel / 13 settings).
+        This is the route for a microphone queue that is still filling;
+        ``tick`` is the one-graph route."""
+        from .data_loaders import mic_front_end, normalised_sensors
+        dev = self.x.device
+        if self.front_end is None:
+            self.front_end = mic_front_end(device=dev)
+        r, d, t = normalised_sensors(force_q, hand_q, depth_q, dev)
+        m = self.front_end.latest(mic_pcm, int(hsr_net.batch_size))[1]
+        return self.score_frames(hsr_net, r, d, t, m)
+
+    # ---- the sensor tick as one replayed graph (mmad_ae_online_tick) ---------
+    def bind_sensors(self, hsr_net, mic_samples, hand_dtype=np.uint8, depth_dtype=np.uint8, front_end=None):
+        """Fix the shapes of ``tick``: the fused ``hsr_net`` (its
+        ``batch_size`` = B <= rows windows a tick), a microphone queue of
+        exactly ``mic_samples`` int16 samples, and the camera queues' element
+        types (uint8 or float32).  Allocates one pinned host staging buffer
+        and its device twin -- PCM int16 [mic_samples] | hand [B][3072] |
+        depth [B][1024] | force fp32 [B], every segment 256-byte aligned --
+        the MFCC outputs, the front end's workspace at its final size and the
+        HSR weights, packed once (``refresh_sensors`` repacks them).
+        front_end: an MfccFrontEnd (None: ``self.front_end``, else the
+        reference's 44.1 kHz / 0.1 s / 128 mel / 13 settings).  A bank binds
+        one set of these for all members and the fused row lands in its
+        shared ``x`` (1728 wide at least); it needs no fused member: a bank of
+        one 'mic' scorer is the unimodal tick."""
+        t = _bind_front(type(self).__name__, self.x, self.rows, hsr_net, mic_samples, hand_dtype, depth_dtype,
+                        front_end or self.front_end, self.norm_division, fused_model=self._fused_model)
+        self.front_end = t["front_end"]
+        if self._fused_model:              # the scorer is the tick's one member
+            _member_args(self, t["args"], t)
+        self._tick = t
+        return self
+
+    def refresh_sensors(self):
+        """Repack the bound HSR_Net's weights into the buffer the tick's graph
+        reads, after its parameters changed: the next ``tick`` sees them, no
+        new capture."""
+        if self._tick is None:
+            raise ValueError(f"{type(self).__name__}.refresh_sensors: call bind_sensors first")
+        self._tick["net"].packed_weights(out=self._tick["weights"])
+
+    def tick(self, force_q, hand_q, depth_q, mic_q):
+        """``score_sensors`` on the shapes ``bind_sensors`` fixed, as one
+        host-to-device copy and one graph launch: the queues are written into
+        the pinned staging buffer with numpy (the first B frames of force,
+        hand and depth, as HSR_Net.forward takes them; all of mic_q: int16
+        samples or the reference's list of ``bytes`` chunks), copied over on
+        the current stream, and the native tick (mmad_ae_online_tick; the
+        bank's mmad_online_bank_tick, for every member) replays MFCC ->
+        fusion -> scoring.  Returns what ``score_sensors`` returns."""
+        who, t = type(self).__name__, self._tick
+        if t is None:
+            raise ValueError(f"{who}.tick: call bind_sensors first")
+        _stage_queues(who, t, force_q, hand_q, depth_q, mic_q)
+        self._tick_native(t["args"])
+        return self._results(t["B"])
+
+
+class OnlineScorer(_SharedRoutes):
     # per-modality scores: off unless ``groups`` is given (then instance attributes)
     groups = None
     group_names = ()
-    front_end = None     # score_sensors' MfccFrontEnd (set one to change its settings)
+    _fused_model = True
 
     def __init__(self, model, nap=None, start_layer_index=0, end_layer_index=None, thresholds=None,
                  rows=ROWS, groups=None):
@@ -329,102 +444,13 @@ class OnlineScorer:
             res["group_flags"] = self.group_flags[:, :B]
         return res
 
-    def score(self, x):
-        """x: [B <= rows, D], host or device.  Returns {'base','sap','nap',
-        'layer_sq','flags'}: views of this object's fixed outputs on the
-        device, rewritten by the next call (copy what you keep).  With groups
-        also 'groups' [G, B] and 'group_flags' [G, B], rows in the order of
-        ``group_names`` (ascending columns)."""
-        x = torch.as_tensor(x)
-        x = x.reshape(x.shape[0], -1)
-        B = x.shape[0]
-        if B > self.rows:
-            raise ValueError(f"OnlineScorer.score: {B} windows > {self.rows}; score_windows "
-                             "(reconstruction_aggregation) is the batch route")
-        if B < 1 or x.shape[1] != self.x.shape[1]:
-            raise ValueError(f"OnlineScorer.score: x must be [1..{self.rows}, {self.x.shape[1]}], got {tuple(x.shape)}")
-        self.x[:B].copy_(x, non_blocking=True)
-        return self._run(B)
-
-    def score_frames(self, hsr_net, r, d, t, m):
-        """One step of get_realtime_dataloader: HSR_Net.forward (mmad_hsr_fuse)
-        of the latest ``hsr_net.batch_size`` <= rows frames straight into the
-        fixed input buffer, on the same stream, then ``score``'s pass."""
-        B = int(hsr_net.batch_size)
-        if B > self.rows:
-            raise ValueError(f"OnlineScorer.score_frames: slicing_size {B} > {self.rows}; score_windows "
-                             "(reconstruction_aggregation) is the batch route")
-        fused = hsr_net.forward(r, d, None, t, m, out=self.x)
+    def _fuse(self, hsr_net, streams, B):
+        fused = hsr_net.forward(*streams, out=self.x)
         if fused.reshape(B, -1).shape[1] != self.x.shape[1]:
             raise ValueError("OnlineScorer.score_frames: the fused row width is not the model's input size")
-        return self._run(B)
 
-    def score_sensors(self, hsr_net, force_q, hand_q, depth_q, mic_pcm):
-        """One tick of the deployment loop from the raw queues
-        (get_realtime_dataloader, utils/data_loaders.py:734-737): norm_vec's
-        fixed-range maps of the camera, depth and force/torque frames
-        (elementwise torch), the microphone's MFCCs and their norm_vec to
-        [-1, 1] over the last ``hsr_net.batch_size`` frames (mmad_mfcc, on the
-        same stream, ahead of the replayed graph), then ``score_frames``.
-        mic_pcm: what MfccFrontEnd takes (``self.front_end``: built on first
-        use with the reference's 44.1 kHz / 0.1 s / 128 mel / 13 settings)."""
-        from .data_loaders import mic_front_end, normalised_sensors
-        dev = self.x.device
-        if self.front_end is None:
-            self.front_end = mic_front_end(device=dev)
-        r, d, t = normalised_sensors(force_q, hand_q, depth_q, dev)
-        m = self.front_end.latest(mic_pcm, int(hsr_net.batch_size))[1]
-        return self.score_frames(hsr_net, r, d, t, m)
-
-    # ---- the sensor tick as one replayed graph (mmad_ae_online_tick) ---------
-    _tick = None         # bind_sensors' buffers and argument struct
-    # norm_vec's quotient inside the tick, read by bind_sensors: 'ieee' (a
-    # correctly rounded division, mmad_hsr_fuse_raw's), 'reciprocal' (the
-    # product with fl(1 / (hi - lo))), or None: whichever of the two torch's
-    # elementwise kernels compute on the scorer's device, so that ``tick``
-    # returns score_sensors' bits (device_divides_by_reciprocal)
-    norm_division = None
-
-    def bind_sensors(self, hsr_net, mic_samples, hand_dtype=np.uint8, depth_dtype=np.uint8, front_end=None):
-        """Fix the shapes of ``tick``: the fused ``hsr_net`` (its
-        ``batch_size`` = B <= rows windows a tick), a microphone queue of
-        exactly ``mic_samples`` int16 samples, and the camera queues' element
-        types (uint8 or float32).  Allocates one pinned host staging buffer
-        and its device twin -- PCM int16 [mic_samples] | hand [B][3072] |
-        depth [B][1024] | force fp32 [B], every segment 256-byte aligned --
-        the MFCC outputs, the front end's workspace at its final size and the
-        HSR weights, packed once (``refresh_sensors`` repacks them).
-        front_end: an MfccFrontEnd (None: ``self.front_end``, else the
-        reference's 44.1 kHz / 0.1 s / 128 mel / 13 settings)."""
-        t = _bind_front("OnlineScorer", self.x, self.rows, hsr_net, mic_samples, hand_dtype, depth_dtype,
-                        front_end or self.front_end, self.norm_division, fused_model=True)
-        self.front_end = t["front_end"]
-        _member_args(self, t["args"], t)
-        self._tick = t
-        return self
-
-    def refresh_sensors(self):
-        """Repack the bound HSR_Net's weights into the buffer the tick's graph
-        reads, after its parameters changed: the next ``tick`` sees them, no
-        new capture."""
-        if self._tick is None:
-            raise ValueError("OnlineScorer.refresh_sensors: call bind_sensors first")
-        self._tick["net"].packed_weights(out=self._tick["weights"])
-
-    def tick(self, force_q, hand_q, depth_q, mic_q):
-        """``score_sensors`` on the shapes ``bind_sensors`` fixed, as one
-        host-to-device copy and one graph launch: the queues are written into
-        the pinned staging buffer with numpy (the first B frames of force,
-        hand and depth, as HSR_Net.forward takes them; all of mic_q: int16
-        samples or the reference's list of ``bytes`` chunks), copied over on
-        the current stream, and mmad_ae_online_tick replays MFCC -> fusion ->
-        scoring.  Returns what ``score_sensors`` returns."""
-        t = self._tick
-        if t is None:
-            raise ValueError("OnlineScorer.tick: call bind_sensors first")
-        _stage_queues("OnlineScorer", t, force_q, hand_q, depth_q, mic_q)
-        self.nat.online_tick(t["args"])
-        return self._results(t["B"])
+    def _tick_native(self, args):
+        self.nat.online_tick(args)
 
     def close(self):
         """Detach the fit from the model."""
@@ -437,7 +463,7 @@ class OnlineScorer:
 SENSOR_KEYS = {"All": None, "hand_camera": "r", "head_depth": "d", "force_torque": "t", "mic": "m"}
 
 
-class SensorBank:
+class SensorBank(_SharedRoutes):
     """Several OnlineScorers -- the fused detector and its unimodal siblings,
     independent models -- scored on ONE shared input row per tick, sharing
     launches (mmad_online_bank_score / _tick; DESIGN.md §4 "Sensor bank"):
@@ -452,9 +478,6 @@ class SensorBank:
     ``tick``): there are no per-member HSR weights, so the unimodal models are
     expected to have been trained on that network's blocks of the fused row."""
 
-    norm_division = None     # as OnlineScorer.norm_division
-    front_end = None
-    _tick = None
     _h = None
 
     def __init__(self, scorers, columns=None, width=None):
@@ -526,85 +549,24 @@ class SensorBank:
     def _results(self, B):
         return {n: s._results(B) for n, s in self.scorers.items()}
 
-    def _run(self, B, graph=True):
+    def _call(self, name, *args):
         from . import _native
         for s in self.scorers.values():
             s.nat.sync_shadow()
-        _native.check(self._lib.mmad_online_bank_score(self._h, self.x.data_ptr(), self.x.stride(0), int(B),
-                                                       self._members, 1 if graph else 0, _native.stream_ptr()),
-                      "mmad_online_bank_score")
+        _native.check(getattr(self._lib, name)(self._h, *args, _native.stream_ptr()), name)
+
+    def _run(self, B, graph=True):
+        self._call("mmad_online_bank_score", self.x.data_ptr(), self.x.stride(0), int(B), self._members,
+                   1 if graph else 0)
         return self._results(B)
 
-    def score(self, x):
-        """x: [B <= rows, W] (W the bank's row width, ``self.x.shape[1]``),
-        host or device.  Returns {name: OnlineScorer.score's dict for
-        x[:, c0:c1]}."""
-        x = torch.as_tensor(x)
-        x = x.reshape(x.shape[0], -1)
-        B = x.shape[0]
-        if B > self.rows:
-            raise ValueError(f"SensorBank.score: {B} windows > {self.rows}; score_windows "
-                             "(reconstruction_aggregation) is the batch route")
-        if B < 1 or x.shape[1] != self.x.shape[1]:
-            raise ValueError(f"SensorBank.score: x must be [1..{self.rows}, {self.x.shape[1]}], got {tuple(x.shape)}")
-        self.x[:B].copy_(x, non_blocking=True)
-        return self._run(B)
-
-    def score_frames(self, hsr_net, r, d, t, m):
-        """OnlineScorer.score_frames for the bank: HSR_Net.forward of the
-        latest frames into the shared row, then the bank's pass."""
-        B = int(hsr_net.batch_size)
-        if B > self.rows:
-            raise ValueError(f"SensorBank.score_frames: slicing_size {B} > {self.rows}; score_windows "
-                             "(reconstruction_aggregation) is the batch route")
+    def _fuse(self, hsr_net, streams, B):
         if hsr_net.unimodal or self.x.shape[1] != 1728:
             raise ValueError("SensorBank.score_frames: a fused HSR_Net and a 1728-wide shared row")
-        hsr_net.forward(r, d, None, t, m, out=self.x)
-        return self._run(B)
+        hsr_net.forward(*streams, out=self.x)
 
-    def score_sensors(self, hsr_net, force_q, hand_q, depth_q, mic_pcm):
-        """OnlineScorer.score_sensors for the bank (a microphone queue that
-        is still filling; ``tick`` is the one-graph route)."""
-        from .data_loaders import mic_front_end, normalised_sensors
-        dev = self.x.device
-        if self.front_end is None:
-            self.front_end = mic_front_end(device=dev)
-        r, d, t = normalised_sensors(force_q, hand_q, depth_q, dev)
-        m = self.front_end.latest(mic_pcm, int(hsr_net.batch_size))[1]
-        return self.score_frames(hsr_net, r, d, t, m)
-
-    def bind_sensors(self, hsr_net, mic_samples, hand_dtype=np.uint8, depth_dtype=np.uint8, front_end=None):
-        """OnlineScorer.bind_sensors for the bank: the same staging buffer,
-        MFCC buffers and packed weights, one set for all members; the fused
-        row lands in the bank's shared ``x`` (1728 wide at least).  The bank
-        needs no fused member: a bank of one 'mic' scorer is the unimodal tick."""
-        t = _bind_front("SensorBank", self.x, self.rows, hsr_net, mic_samples, hand_dtype, depth_dtype,
-                        front_end or self.front_end, self.norm_division)
-        self.front_end = t["front_end"]
-        self._tick = t
-        return self
-
-    def refresh_sensors(self):
-        """Repack the bound HSR_Net's weights into the buffer the bank's graph
-        reads: the next ``tick`` sees them, no new capture."""
-        if self._tick is None:
-            raise ValueError("SensorBank.refresh_sensors: call bind_sensors first")
-        self._tick["net"].packed_weights(out=self._tick["weights"])
-
-    def tick(self, force_q, hand_q, depth_q, mic_q):
-        """One sensor tick for every member: one host-to-device copy and one
-        graph launch (mmad_online_bank_tick: MFCC -> fusion -> the bank's
-        pass).  Returns {name: what that scorer's ``tick`` returns}."""
-        from . import _native
-        t = self._tick
-        if t is None:
-            raise ValueError("SensorBank.tick: call bind_sensors first")
-        _stage_queues("SensorBank", t, force_q, hand_q, depth_q, mic_q)
-        for s in self.scorers.values():
-            s.nat.sync_shadow()
-        _native.check(self._lib.mmad_online_bank_tick(self._h, ctypes.byref(t["args"]), self._members, 1,
-                                                      _native.stream_ptr()), "mmad_online_bank_tick")
-        return self._results(t["B"])
+    def _tick_native(self, args):
+        self._call("mmad_online_bank_tick", ctypes.byref(args), self._members, 1)
 
     def close(self):
         """Drop the bank's captured graphs and native object (the scorers,

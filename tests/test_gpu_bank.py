@@ -107,6 +107,70 @@ def test_bank_equals_its_scorers(models, windows, rows, Bs):
     bank.close()
 
 
+def chain(widths, vib, seed):
+    """An fp32 autoencoder whose encoder runs through ``widths`` (the decoder back again)."""
+    from icra2021_multimodal_ad_amd.auto_encoder import AutoEncoder
+    from icra2021_multimodal_ad_amd.fc_module import FCModule, Loss
+    torch.manual_seed(seed)
+    d, btl, hidden = widths[0], widths[-1], list(widths[1:-1])
+    fc = dict(use_batch_norm=True, act="leakyrelu", last_act=None)
+    m = AutoEncoder(encoder=FCModule(input_size=d, output_size=2 * btl if vib else btl, hidden_sizes=hidden, **fc),
+                    decoder=FCModule(input_size=btl, output_size=d, hidden_sizes=hidden[::-1], **fc),
+                    recon_loss=Loss("mse", reduction="sum"), vib=vib).cuda(0)
+    m.eval()
+    return m
+
+
+def buffers(sc):
+    """A scorer's whole output buffers (the canaries a call leaves included)."""
+    bufs = {"out": sc.out, "flags": sc.flags}
+    if sc.groups is not None:
+        bufs.update(group_out=sc.group_out, group_flags=sc.group_flags)
+    return {k: v.clone() for k, v in bufs.items()}
+
+
+@pytest.mark.parametrize("rows,B", [(16, 3), (64, 17)])
+@pytest.mark.parametrize("widths", [((128, 64), (128, 64, 32), (128, 64, 32, 16)),
+                                    ((128, 16), (128, 32, 64), (128, 16, 64, 32))], ids=["halving", "mixed"])
+def test_members_run_out_of_steps_at_different_points(windows, widths, rows, B):
+    """Three fp32 members of 1, 2 and 3 encoder layers on one 128-column row:
+    pass 1 has 2 / 4 / 6 steps and pass 2 has 1 / 2 / 3, so every step from the
+    third on is absent for a neighbour, and the VIB launch of the middle member
+    lands between two grouped steps.  The shallow member has two groups, the
+    deep one an fp32 NAP fit.  Eagerly, on the capturing call and replayed,
+    every member's out, flags, group_out and group_flags are, bit for bit,
+    what its own scorer's ``score`` leaves there."""
+    one, two, three = (chain(w, vib=i == 1, seed=40 + i) for i, w in enumerate(widths))
+    scs = {"one": OnlineScorer(one, rows=rows, groups=[(0, 64), (64, 128)],
+                               thresholds={"base": 0.05, "sap": 0.05, "groups": {0: 0.05, 1: -1.0}}),
+           "two": OnlineScorer(two, rows=rows),
+           "three": OnlineScorer(three, _fit(three, (0, 4)), rows=rows,
+                                 thresholds={"base": 0.05, "sap": 0.05, "nap": 1.0})}
+    assert [sc.nat.n_enc for sc in scs.values()] == [1, 2, 3] and scs["two"].nat.vib
+    assert scs["one"].groups == [0, 64, 128] and scs["three"].nap is not None
+    bank = SensorBank(scs)                                   # every member reads columns 0..128
+    assert bank.x.shape == (rows, 128)
+    x = windows[:B, :128]
+    want = {}
+    for name, sc in scs.items():
+        poison(sc)
+        sc.score(x)
+        want[name] = buffers(sc)
+    for graph in (False, True, True):                        # eager, the capturing call, a replay
+        for sc in scs.values():
+            poison(sc)
+        bank.x[:B].copy_(x)
+        bank._run(B, graph=graph)
+        torch.cuda.synchronize()
+        for name, sc in scs.items():
+            got = buffers(sc)
+            assert set(got) == set(want[name])
+            for k in got:
+                assert torch.equal(got[k], want[name][k]), (name, k, graph)
+    assert bank.graph_count() == 1
+    bank.close()
+
+
 def launches(nat, groups=False):
     """The single pass's launch list: pack, fold, one per layer, one per
     encoder layer again, (VIB, group_sq, NAP), finish."""
