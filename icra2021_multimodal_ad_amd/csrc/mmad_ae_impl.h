@@ -1,8 +1,8 @@
 // Internal (non-ABI) state of the whole-autoencoder executor: the handle, the
-// workspace carve and the helpers shared by mmad_ae.hip (lifecycle, workspace,
-// training executor), mmad_ae_score.hip (batch / streaming score path, NAP
-// fit) and mmad_ae_online.hip (16-row online path), plus the one
-// capture-and-replay cache behind their hipGraph paths.
+// workspace carve and the helpers shared by mmad_ae.hip (lifecycle, workspace, forward, Adam,
+// status, probe), mmad_ae_train.hip (training executor, data parallel), mmad_ae_score.hip
+// (batch / streaming score path, NAP fit) and mmad_ae_online.hip (16-row online path), plus
+// the one capture-and-replay cache behind their hipGraph paths.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -230,6 +230,143 @@ struct AeSchedule {
   bool splitk_ws = false;
 };
 
+// Move-only owner of one HIP resource (an event, a stream, a pinned
+// allocation): null by default, converts to the raw handle, released with D
+template <class T, auto D>
+class Owned {
+ public:
+  Owned() = default;
+  Owned(Owned&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  Owned& operator=(Owned&& o) noexcept { std::swap(p_, o.p_); return *this; }   // o releases the old one
+  ~Owned() { reset(); }
+  operator T() const { return p_; }
+  T* put() { reset(); return &p_; }   // the out-parameter of a create call
+  void reset() { if (p_) (void)D(p_); p_ = nullptr; }
+ private:
+  T p_ = nullptr;
+};
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+
+// `ev` recorded on `from`, waited for on `to`
+inline int hand_off(hipEvent_t ev, hipStream_t from, hipStream_t to) {
+  MMAD_HIP_CHECK(hipEventRecord(ev, from));
+  MMAD_HIP_CHECK(hipStreamWaitEvent(to, ev, 0));
+  return MMAD_OK;
+}
+
+// side stream + events for the dW / Adam overlap (created at bind time)
+struct SideState {
+  Stream stream;
+  std::vector<Event> ev_fork, ev_data;
+  Event ev_join;
+  Event ev_loss;   // fused step: forward done -> the loss reduction on the side stream
+  Event ev_hold;   // sched.side_hold: the bwd-data chain is enqueued
+  int create(const AeSchedule& sched, size_t n_layers);   // all or nothing (mmad_ae.hip)
+};
+
+struct DpState {
+  // sharded data-parallel steps (sched.dp_shard): the bf16 model's fp32 master
+  // weights / every model's Adam moments are current only on their owning
+  // rank since the last mmad_ae_dp_sync_master
+  bool master_stale = false;
+  // data parallelism: RCCL communicator (not owned), its stream and events
+  mmad_comm* comm = nullptr;
+  Stream cstream;
+  std::vector<Event> ev_dw;
+  Event ev_small, ev_cdone;
+  // torch-exchange data parallelism (mmad_ae_dw_events): the forward+backward
+  // without Adam records ev_xdw[l] after dW_l and ev_xdata[l] after bwd-data of
+  // l.  System-scope fences (unlike the executor's own events): the exchange
+  // may read the gradients with a copy engine, which does not see the L2
+  bool dw_events = false;
+  std::vector<Event> ev_xdw, ev_xdata;
+  // optional bf16 gradient exchange (mmad_ae_set_grad_bf16): n_weight bf16
+  void* grad_bf16 = nullptr;
+  // the comm stream and its events / the torch-exchange events: each built in a local, moved in when complete
+  int create_comm(const AeSchedule& sched, size_t n_layers) {
+    DpState d;
+    // highest priority: the exchange must not queue behind the dW GEMMs
+    int least = 0, greatest = 0;
+    MMAD_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    MMAD_HIP_CHECK(hipStreamCreateWithPriority(d.cstream.put(), hipStreamNonBlocking, greatest));
+    // the events RCCL's reads of a bucket wait on keep the system-scope
+    // fence (a transport may move the bytes with a copy engine, which does
+    // not see the L2); one per bucket and step
+    d.ev_dw.resize(n_layers);
+    for (Event& e : d.ev_dw) MMAD_HIP_CHECK(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+    MMAD_HIP_CHECK(hipEventCreateWithFlags(d.ev_small.put(), hipEventDisableTiming));
+    MMAD_HIP_CHECK(hipEventCreateWithFlags(d.ev_cdone.put(), sched.ev_flags_));
+    cstream = std::move(d.cstream), ev_dw = std::move(d.ev_dw);
+    ev_small = std::move(d.ev_small), ev_cdone = std::move(d.ev_cdone);
+    return MMAD_OK;
+  }
+  int create_dw_events(size_t n_layers) {
+    std::vector<Event> xdw(n_layers), xdata(n_layers);
+    for (Event& e : xdw) MMAD_HIP_CHECK(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+    for (Event& e : xdata) MMAD_HIP_CHECK(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+    ev_xdw = std::move(xdw), ev_xdata = std::move(xdata);
+    return MMAD_OK;
+  }
+};
+
+// kernel probe (mmad_ae_probe): timing events around ONE GEMM launch of
+// the step, on the stream it is launched on (bench roofline, in situ)
+struct Probe {
+  int id = -1, n = 0;
+  unsigned mask = 0;        // layers the last probed launch covered (bit l)
+  std::vector<Event> ev;    // [2 * capacity]: start, end pairs
+  Event sync;               // a main-stream probe's start waits for the side stream
+  // probe kinds 2 / 3: the events ride on the launch itself (hipExtLaunchKernel
+  // start / stop: the kernel's own start and end, as rocprofv3's kernel records)
+  // and nothing waits for the side stream -- the launch as it runs in the
+  // step's schedule, so the probe can stay on through a timed region
+  bool kev = false;
+  // One launch on `s`, bracketed if it is the probed one (`hit`) and the probe has room: launch(start, stop)
+  // issues it, with the two events to attach to it or nulls.  layers: the mask a bracketed launch leaves.
+  // No probe under capture; has_done_ev: the launch carries a hand-off event already
+  template <class Launch>
+  int bracket(bool hit, unsigned layers, bool capturing, hipStream_t s, hipStream_t side, bool has_done_ev,
+              Launch launch) {
+    const bool rec = hit && !capturing && 2 * n < (int)ev.size();
+    if (rec && !kev && side && s != side && sync) {
+      // a probed main-stream launch starts its clock once the side stream's
+      // earlier GEMMs are done: its blocks (a whole CU's LDS each on the tail
+      // tiles) wait for those CUs anyway, and the event pair then brackets the
+      // launch's own execution, first dispatch to completion, as rocprofv3's
+      // kernel records do (without it the pair also held ~4 us of that wait on
+      // the c2 tail: 31.2 vs 26.8 us, profiles/r08o_prof_c2)
+      RET_IF(hand_off(sync, side, s));
+    }
+    // kernel-attached events only where the launch carries no hand-off event
+    const bool attach = rec && kev && !has_done_ev;
+    if (rec && !attach) MMAD_HIP_CHECK(hipEventRecord(ev[2 * n], s));
+    const int rc = attach ? launch(ev[2 * n], ev[2 * n + 1]) : launch(nullptr, nullptr);
+    if (rc != MMAD_OK) return rc;
+    if (rec) {
+      if (!attach) MMAD_HIP_CHECK(hipEventRecord(ev[2 * n + 1], s));
+      ++n;
+      mask = layers;
+    }
+    return MMAD_OK;
+  }
+};
+
+// hipGraph-captured fused train steps (mmad_ae_train_step_graph): one per
+// call signature, replayed after a host->device copy of the per-call values
+// (a ring of pinned host slots, each reused only once its copy has run)
+struct TrainGraphs {
+  GraphCache<TrainKey> graphs{16};
+  static constexpr int kDynSlots = 64;
+  Owned<MmadDyn*, hipHostFree> dyn_host;
+  Event dyn_ev[kDynSlots];
+  bool dyn_used[kDynSlots] = {};
+  int dyn_next = 0;
+  bool broken = false;
+  // this call's values -> the next pinned slot -> dev, on st (the ring: made on first use, all or nothing)
+  int stage(const MmadDyn& d, MmadDyn* dev, unsigned ev_flags, hipStream_t st);
+};
+
 }  // namespace mmad_ae_impl
 
 struct mmad_ae {
@@ -243,6 +380,30 @@ struct mmad_ae {
   // shadow_alt while this step's backward still reads shadow, then the two
   // swap; so a dW GEMM need not wait for its layer's bwd-data GEMM
   void* shadow_alt = nullptr;
+  // the schedule (tune-table knobs 14-31, 33-35 and the split-K slab decision),
+  // fixed at create
+  mmad_ae_impl::AeSchedule sched;
+  int mse_tiles = 0;   // loss partials written by the last MSE GEMM
+  // ping-pong steps (mmad_ae_set_dw_group): consecutive side-stream layers
+  // whose dW + Adam GEMM takes the 64x64 tile are issued as ONE grouped launch
+  // (mmad_gemm_dispatch_group) at the lowest member's fork -- at 4096 rows
+  // each of the narrow layers' launches is one block's 64-stage K loop,
+  // 23-25 us for 16 to 135 blocks, and they ran back to back.  blocks = the
+  // group's budget of padded blocks (0 = off: every dW its own launch; < 0 =
+  // one resident round of the kernel), members = at most this many per group
+  int dw_group_blocks = MMAD_DW_GROUP_BLOCKS_DEFAULT;
+  int dw_group_members = MMAD_GEMM_GROUP_MAX;
+  // a capture of one of the three caches' passes is open on gstream
+  // (capture_graph): no timing probe, no kernel-attached hand-off events
+  bool capturing = false;
+  // workspace whose split-K control block this handle has zeroed
+  const void* ws_zeroed = nullptr;
+  mmad_ae_impl::SideState side;
+  mmad_ae_impl::DpState dp;
+  mmad_ae_impl::Probe probe;
+  mmad_ae_impl::Stream gstream;   // capture stream (the caller's may be the null stream)
+  // the three graph caches after gstream: destroyed ahead of the stream they were captured on
+  mmad_ae_impl::TrainGraphs train;
   // split-bf16 scoring (mmad_ae_set_score_planes, F32 handles): bf16
   // [2][n_weight] weight planes; the eval forward / score GEMMs then run as
   // MMAD_BF16X3.  planes_stale: the fp32 weights were (or may have been)
@@ -260,42 +421,6 @@ struct mmad_ae {
     const float *vt = nullptr, *bias = nullptr, *w = nullptr;
     void* vt_planes = nullptr;
   } nap;
-  // side stream + events for the dW / Adam overlap (created at bind time)
-  hipStream_t side = nullptr;
-  std::vector<hipEvent_t> ev_fork, ev_data;
-  hipEvent_t ev_join = nullptr;
-  hipEvent_t ev_loss = nullptr;   // fused step: forward done -> the loss reduction on the side stream
-  // the schedule (tune-table knobs 14-31, 33-35 and the split-K slab decision),
-  // fixed at create
-  mmad_ae_impl::AeSchedule sched;
-  // sharded data-parallel steps (sched.dp_shard): the bf16 model's fp32 master
-  // weights / every model's Adam moments are current only on their owning
-  // rank since the last mmad_ae_dp_sync_master
-  bool master_stale = false;
-  int mse_tiles = 0;   // loss partials written by the last MSE GEMM
-  // data parallelism: RCCL communicator (not owned), its stream and events
-  mmad_comm* comm = nullptr;
-  hipStream_t cstream = nullptr;
-  std::vector<hipEvent_t> ev_dw;
-  // torch-exchange data parallelism (mmad_ae_dw_events): the forward+backward
-  // without Adam records ev_xdw[l] after dW_l and ev_xdata[l] after bwd-data of
-  // l.  System-scope fences (unlike the executor's own events): the exchange
-  // may read the gradients with a copy engine, which does not see the L2
-  bool dw_events = false;
-  std::vector<hipEvent_t> ev_xdw, ev_xdata;
-  // optional bf16 gradient exchange (mmad_ae_set_grad_bf16): n_weight bf16
-  void* grad_bf16 = nullptr;
-  hipEvent_t ev_small = nullptr, ev_cdone = nullptr;
-  hipEvent_t ev_hold = nullptr;   // sched.side_hold: the bwd-data chain is enqueued
-  // ping-pong steps (mmad_ae_set_dw_group): consecutive side-stream layers
-  // whose dW + Adam GEMM takes the 64x64 tile are issued as ONE grouped launch
-  // (mmad_gemm_dispatch_group) at the lowest member's fork -- at 4096 rows
-  // each of the narrow layers' launches is one block's 64-stage K loop,
-  // 23-25 us for 16 to 135 blocks, and they ran back to back.  blocks = the
-  // group's budget of padded blocks (0 = off: every dW its own launch; < 0 =
-  // one resident round of the kernel), members = at most this many per group
-  int dw_group_blocks = MMAD_DW_GROUP_BLOCKS_DEFAULT;
-  int dw_group_members = MMAD_GEMM_GROUP_MAX;
   // hipGraph cache for mmad_ae_score_stream: one captured graph per
   // (input, output, workspace, N, batch) pass, replayed with one launch
   mmad_ae_impl::GraphCache<mmad_ae_impl::ScoreKey> graphs{8};
@@ -306,59 +431,6 @@ struct mmad_ae {
   // both ways, or two states taking turns, are zeroed again at each change
   mmad_ae_impl::GraphCache<mmad_ae_impl::OnlineKey> ographs{8};
   const void* online_ready = nullptr;
-  // kernel probe (mmad_ae_probe): timing events around ONE GEMM launch of
-  // the step, on the stream it is launched on (bench roofline, in situ)
-  mutable int probe_id = -1;
-  mutable int probe_n = 0;
-  mutable unsigned probe_mask = 0;    // layers the last probed launch covered (bit l)
-  std::vector<hipEvent_t> probe_ev;   // [2 * capacity]: start, end pairs
-  hipEvent_t probe_sync = nullptr;    // a main-stream probe's start waits for the side stream
-  // probe kinds 2 / 3: the events ride on the launch itself (hipExtLaunchKernel
-  // start / stop: the kernel's own start and end, as rocprofv3's kernel records)
-  // and nothing waits for the side stream -- the launch as it runs in the
-  // step's schedule, so the probe can stay on through a timed region
-  bool probe_kev = false;
-  // hipGraph-captured fused train steps (mmad_ae_train_step_graph): one per
-  // call signature, replayed after a host->device copy of the per-call values
-  // (a ring of pinned host slots, each reused only once its copy has run)
-  mmad_ae_impl::GraphCache<mmad_ae_impl::TrainKey> tgraphs{16};
-  static constexpr int kDynSlots = 64;
-  MmadDyn* dyn_host = nullptr;
-  hipEvent_t dyn_ev[kDynSlots] = {};
-  bool dyn_used[kDynSlots] = {};
-  int dyn_next = 0;
-  // a capture of one of the three caches' passes is open on gstream
-  // (capture_graph): no timing probe, no kernel-attached hand-off events
-  bool capturing = false;
-  bool graph_broken = false;
-  // workspace whose split-K control block this handle has zeroed
-  const void* ws_zeroed = nullptr;
-  hipStream_t gstream = nullptr;   // capture stream (the caller's may be the null stream)
-  ~mmad_ae() {
-    // the captured graphs go ahead of the stream they were captured on (the
-    // members' own destructors would run after this body)
-    tgraphs.clear();
-    for (auto e : dyn_ev)
-      if (e) (void)hipEventDestroy(e);
-    if (dyn_host) (void)hipHostFree(dyn_host);
-    for (auto e : probe_ev) (void)hipEventDestroy(e);
-    if (probe_sync) (void)hipEventDestroy(probe_sync);
-    graphs.clear();
-    ographs.clear();
-    if (gstream) (void)hipStreamDestroy(gstream);
-    for (auto e : ev_fork) (void)hipEventDestroy(e);
-    for (auto e : ev_data) (void)hipEventDestroy(e);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (ev_hold) (void)hipEventDestroy(ev_hold);
-    if (ev_loss) (void)hipEventDestroy(ev_loss);
-    for (auto e : ev_dw) (void)hipEventDestroy(e);
-    for (auto e : ev_xdw) (void)hipEventDestroy(e);
-    for (auto e : ev_xdata) (void)hipEventDestroy(e);
-    if (ev_small) (void)hipEventDestroy(ev_small);
-    if (ev_cdone) (void)hipEventDestroy(ev_cdone);
-    if (cstream) (void)hipStreamDestroy(cstream);
-    if (side) (void)hipStreamDestroy(side);
-  }
 };
 
 namespace mmad_ae_impl {
@@ -427,7 +499,7 @@ inline float* running_var(const mmad_ae* h, const AeLayer& a) {
 
 // mmad_ae.hip
 void carve(const mmad_ae* h, int B, int k, char* base, AeWS& w);
-int prepare_ws(const mmad_ae* h, int B, int k, void* ws, int64_t ws_bytes, AeWS& w, hipStream_t st);
+int prepare_ws(mmad_ae* h, int B, int k, void* ws, int64_t ws_bytes, AeWS& w, hipStream_t st);
 int refresh_planes(mmad_ae* h, hipStream_t st, bool force = false);
 const void* weights(const mmad_ae* h, const AeLayer& a);
 const void* weights_dt(const mmad_ae* h, const AeLayer& a, int dt, GemmEpi& ep);
@@ -435,9 +507,17 @@ const void* input_of(const mmad_ae* h, const AeWS& w, int l, bool train, const f
                      const float** shift);
 GemmEpi fwd_epi(const mmad_ae* h, const AeWS& w, const AeLayer& a, const LayerWS& s, int M, void* out,
                 bool folded);
-int ae_gemm(const mmad_ae* h, const AeWS& w, int dt, int epi, const void* A, int lda, const void* B,
+int ae_gemm(mmad_ae* h, const AeWS& w, int dt, int epi, const void* A, int lda, const void* B,
             int ldb, int Mp, int Np, int K, GemmEpi ep, hipStream_t s, int* cfg = nullptr,
             int probe = -1);
+// probe ids: PROBE_FWD + layer (forward / MSE / score GEMM of the layer),
+// PROBE_DW + layer (its dW GEMM, with the fused Adam in the fused step)
+enum { PROBE_FWD = 0, PROBE_DW = 64 };
+// the forward: train with the MSE-fused last layer, eval, or train BN with a plain last layer
+enum class FwdMode { TrainMse, Eval, TrainBnPlain };
+// mse_done (nullable): an event the train-mode MSE GEMM launch completes itself
+int run_forward(mmad_ae* h, AeWS& w, const float* x, int ld_x, FwdMode mode, const float* eps, uint64_t seed,
+                uint64_t offset, hipStream_t st, hipEvent_t mse_done = nullptr);
 // mmad_ae_score.hip
 int diff_col(const mmad_ae* h, int j);
 
@@ -457,10 +537,10 @@ struct GraphCaptureResult {
 // the capture itself, on *gstream (created on first use); kernel_nodes, if
 // given, receives the captured graph's kernel-node count
 template <class Pass>
-GraphCaptureResult capture_graph_on(hipStream_t* gstream, Pass pass, hipGraphExec_t* exec,
+GraphCaptureResult capture_graph_on(Stream* gstream, Pass pass, hipGraphExec_t* exec,
                                     int* kernel_nodes = nullptr) {
   *exec = nullptr;
-  hipError_t e = *gstream ? hipSuccess : hipStreamCreateWithFlags(gstream, hipStreamNonBlocking);
+  hipError_t e = *gstream ? hipSuccess : hipStreamCreateWithFlags(gstream->put(), hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamBeginCapture(*gstream, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) return {GC_BEGIN, MMAD_OK, e};
   const int rc = pass(*gstream);

@@ -374,13 +374,9 @@ struct mmad_online_bank {
   int n = 0, rows = 0;
   mmad_ae* h[MMAD_MAX_BANK] = {};
   int col0[MMAD_MAX_BANK] = {};
+  Stream gstream;             // capture stream; ahead of the graphs captured on it, destroyed after them
   GraphCache<BankKey> graphs{8};
-  hipStream_t gstream = nullptr;   // capture stream
-  int nodes = 0;                   // kernel nodes of the last captured pass
-  ~mmad_online_bank() {
-    graphs.clear();
-    if (gstream) (void)hipStreamDestroy(gstream);
-  }
+  int nodes = 0;              // kernel nodes of the last captured pass
 };
 
 // the launches of a checked call -- (front: a tick's front launches, then) the
