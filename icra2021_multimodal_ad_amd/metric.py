@@ -102,8 +102,16 @@ def get_f1_score(valid_score, test_score, test_label, f1_quantiles=(.99,)):
 
 
 def get_confusion_matrix(score, test_label, threshold):
-    """utils/metric.py:83-95 (returns precision, recall at score >= threshold)."""
-    r = threshold_metrics(np.asarray([threshold], np.float32), score, test_label, 0.0)
+    """utils/metric.py:83-95 (returns precision, recall at score >= threshold).
+    The reference compares fp32 scores with the caller's float64 threshold; for
+    an fp32 score s, s >= t holds exactly when s >= the smallest fp32 value
+    that is >= t, so the threshold is rounded up to fp32, not to nearest."""
+    t = float(threshold)
+    with np.errstate(over="ignore"):
+        t32 = np.float32(t)
+    if float(t32) < t:
+        t32 = np.nextafter(t32, np.float32(np.inf))
+    r = threshold_metrics(np.asarray([t32], np.float32), score, test_label, 0.0)
     return r[4], r[5]
 
 

@@ -948,7 +948,12 @@ int mmad_rank_metrics(int64_t n, const float* score, const uint8_t* label, doubl
 /* get_f1_score :118-130 (threshold = np.quantile(valid, q), linear rule;
  * prediction test > threshold) and get_confusion_matrix :83-95 (test >=
  * threshold): out[10] = threshold, f1, p, r, precision, recall, tp, fp, fn,
- * tn (undefined ratios are NaN, as numpy's 0/0). */
+ * tn (undefined ratios are NaN, as numpy's 0/0).  The quantile is the linear
+ * rule taken in float64 (virtual index q (n_valid - 1), numpy's _lerp between
+ * the two neighbours) and rounded once to fp32:
+ * float32(np.quantile(float64(valid), q)).  numpy's own path for a float32
+ * array forms the index and the interpolation in fp32 and can land some fp32
+ * steps away; the threshold returned is the one the counts were taken at. */
 size_t mmad_threshold_metrics_ws_bytes(int64_t n_valid);
 int mmad_threshold_metrics(int64_t n_valid, const float* valid, int64_t n_test, const float* test,
                            const uint8_t* label, double q, double* out, void* ws, size_t ws_bytes,

@@ -106,6 +106,31 @@ def test_operator_entries_refuse_unknown_dtype(lib):
         assert b"MMAD_BF16X3 covers the eval / score path only" in err(), (name, err())
 
 
+def test_metric_entries_refuse_bad_arguments_before_any_device_call(lib):
+    """mmad_rank_metrics / mmad_threshold_metrics check n, n_test, q and the
+    pointers on the host before they size anything: MMAD_EINVAL with the
+    entry's name, nothing behind the pointers read or written, no GPU needed.
+    (Their workspace checks come after rocPRIM's size queries, which ask for
+    the device: tests/test_gpu_metrics.py has those.)"""
+    buf = ctypes.create_string_buffer(b"\xa5" * 1024, 1024)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 255) // 256 * 256)
+    err = lib.mmad_last_error_string
+    rank = [10, p, p, p, p, 1 << 20, None]
+    for i, v in ((0, 0), (0, -1), (0, 1 << 31), (1, None), (2, None), (3, None), (4, None)):
+        bad = list(rank)
+        bad[i] = v
+        assert lib.mmad_rank_metrics(*bad) == -1, (i, v)
+        assert b"rank_metrics: bad arguments" in err(), err()
+    thr = [10, p, 5, p, p, 0.9, p, p, 1 << 20, None]
+    for i, v in ((0, 0), (0, 1 << 31), (2, 0), (2, -3), (1, None), (3, None), (4, None), (6, None), (7, None),
+                 (5, -0.1), (5, 1.1), (5, float("nan"))):
+        bad = list(thr)
+        bad[i] = v
+        assert lib.mmad_threshold_metrics(*bad) == -1, (i, v)
+        assert b"threshold_metrics: bad arguments" in err(), err()
+    assert buf.raw == b"\xa5" * 1024
+
+
 def test_tune_table_names_and_defaults(lib):
     """_native.KNOB names exactly the knobs include/mmad.h documents (a slot
     past the table is refused), and the table starts at the documented
